@@ -29,6 +29,14 @@ sub-controllers per GPU of S_total = 8 x world per scenario, the plans
 all-gathered over RCCL once per Jacobi iteration; `coupled_s64` runs config
 4's own 64-sub-controller system at every world size (64 / world per GPU).
 
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up,
+times the K steps, writes the last timed step's outputs with --dump-outputs
+DIR, and prints the result line.  Everything else measured here (the iterate
+kernel's own pass, working-set traces, the harder-QP, K = 1, closed-loop,
+SURVEY-config, recorded-run and coupled sections, the CPU baseline, the PMC
+traffic lookup) runs after that with --full; their keys are null in a plain
+run's line (`cpu_baseline` is left out, as with --no-cpu).
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -521,6 +529,30 @@ def spawn_ranks(n: int, argv, script=None) -> int:
             signal.signal(s, h)
 
 
+DUMP_LIMIT_BYTES = 60 * 10**6   # all files of one --dump-outputs directory
+
+
+def dump_outputs(path, rank, world, arrays):
+    """--dump-outputs: each array (one row per QP) as path/<name>.npy in
+    float64 (rank r > 0: <name>.rank<r>.npy).  Past this rank's share of
+    DUMP_LIMIT_BYTES the same fixed, seeded sample of rows of every array,
+    their indices in rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    row_bytes = 8 + sum(8 * (a.size // n) for a in arrays.values())
+    keep = None
+    limit = DUMP_LIMIT_BYTES // world
+    if n * row_bytes > limit:
+        keep = np.sort(np.random.default_rng(6401).choice(n, limit // row_bytes, replace=False))
+        arrays = dict(arrays, rows=keep)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if keep is not None and name != "rows":
+            a = a[keep]
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"), a)
+    log(f"[rank {rank}] outputs of the last timed step: {sorted(arrays)} in {path}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -535,9 +567,21 @@ def main():
                     help="untimed steps after the W warmup steps until this much wall time has "
                          "passed: the chip ramps its clock over the first ~40 ms of this load "
                          "(tools/time_clock_ramp.py), and the metric is the steady state")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything else the benchmark measures: the iterate "
+                         "kernel's own pass, working-set traces, harder-QP, K = 1, closed-loop, SURVEY "
+                         "configs, recorded-run, coupled and CPU-baseline sections and the PMC traffic "
+                         "lookup.  Off by default: a plain run sets up, warms up, times --steps steps, "
+                         "writes --dump-outputs and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (move plans, "
+                         "QP status, working-set changes, and its batch's u_old with the first move "
+                         "applied and the working sets it leaves for the next step) "
+                         "as DIR/<name>.npy, float64")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the metric's steps (no K = 1, closed-loop, coupled or CPU sections): "
+                    help="with --full: only the metric's steps and the kernels' own passes (no K = 1, "
+                         "closed-loop, coupled or CPU sections): "
                          "profiler runs, so that every build launch in the trace is a headline one")
     ap.add_argument("--markers", action="store_true",
                     help="a torch.cuda._sleep launch before and after the timed steps and before and "
@@ -572,6 +616,11 @@ def main():
                          "(an RCCL communicator of one rank: exercises the multi-GPU code path "
                          "on a one-GPU box)")
     args = ap.parse_args()
+    if not args.full and (args.headline_only or args.configs_only or args.build_events == "separate"):
+        ap.error("--headline-only, --configs-only and --build-events separate select among the "
+                 "sections of a --full run: pass --full with them")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     def device_count():
         import torch  # device_count() does not initialise the GPU (no HIP context)
@@ -659,6 +708,14 @@ def main():
             ctx.step(K, 0)
             settle_steps += 1
         ctx.synchronize()
+    # whole rotations of the batches (already so when NB divides 16): the timed
+    # steps then start on the same batch in every run, whatever the settle
+    # phase's step count was, and so does their last step (--dump-outputs)
+    while settle_steps % NB:
+        bind(args.warmup + settle_steps)
+        ctx.step(K, 0)
+        settle_steps += 1
+    ctx.synchronize()
     t_settle = time.perf_counter() - t_settle
     # the timed steps continue the batch rotation where the warmup left it
     first = args.warmup + settle_steps
@@ -698,9 +755,10 @@ def main():
         dist.barrier()
     build_ms, n_build = ctx.kernel_time(cmpc.CMPC_KERNEL_BUILD)
     ctx.set_timing_stride(1)
-    if n_build == 0 and args.build_events == "timed":
+    if args.full and n_build == 0 and args.build_events == "timed":
         # the steps ran fused (a small --batch, CMPC_STEP_AUTO): the build
         # kernel's own launch time from a build-only pass for the roofline
+        # (a plain run reports no build roofline then)
         ctx.enable_timing(True, only=(cmpc.CMPC_KERNEL_BUILD,))
         for i in range(args.steps):
             bind(first + i)
@@ -721,7 +779,14 @@ def main():
 
     du, st, nw = ctx.download()
     u_drift = max(float((st_[0] - sn[0]).abs().max()) for st_, sn in zip(states, snap))
-    ws_now = states[(first + args.steps - 1) % NB][2].cpu().numpy()  # the last step's batch
+    last = states[(first + args.steps - 1) % NB]  # the last step's batch
+    ws_now = last[2].cpu().numpy()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world,
+                     {"du": du, "status": st, "working_set_changes": nw, "u_old": last[0].cpu().numpy(),
+                      "working_set": ws_now.view(np.uint32)})
+    # a plain run ends with its result line; everything below measures more
+    extras = args.full and not args.headline_only
 
     def restore(warm=False):
         """The states of the timed steps' start; warm: then build-only
@@ -743,15 +808,17 @@ def main():
     # the iterate kernel's own time: the same step loop from the same states,
     # events on the iterate only (after the headline measurement, untimed for
     # `value`)
-    restore(warm=True)
-    marker()
-    ctx.enable_timing(True, only=(cmpc.CMPC_KERNEL_ITERATE,))
-    for i in range(args.steps):
-        bind(first + i)
-        ctx.step(K, cmpc.CMPC_APPLY_MOVE)
-    ctx.synchronize()
-    iter_ms, n_iter = ctx.kernel_time(cmpc.CMPC_KERNEL_ITERATE)
-    marker()
+    iter_ms, n_iter = 0.0, 0
+    if args.full:
+        restore(warm=True)
+        marker()
+        ctx.enable_timing(True, only=(cmpc.CMPC_KERNEL_ITERATE,))
+        for i in range(args.steps):
+            bind(first + i)
+            ctx.step(K, cmpc.CMPC_APPLY_MOVE)
+        ctx.synchronize()
+        iter_ms, n_iter = ctx.kernel_time(cmpc.CMPC_KERNEL_ITERATE)
+        marker()
     if args.build_events == "separate":
         # the build's launch time from a second pass of the timed steps
         restore(warm=True)
@@ -762,12 +829,13 @@ def main():
         ctx.synchronize()
         build_ms, n_build = ctx.kernel_time(cmpc.CMPC_KERNEL_BUILD)
     ctx.enable_timing(False)
-    restore()
+    if args.full:
+        restore()
     # working-set changes of the timed workload, summed over the K Jacobi
     # iterations and all QPs of a step (CMPC_TRACE counts, untimed pass over
     # one rotation of the batches)
     ws_changes = ws_changes_steps = None
-    if not args.headline_only:  # (profiler runs: every build launch a headline one, no traced solves)
+    if extras:  # (profiler runs: every build launch a headline one, no traced solves)
         # a traced replay of the timed steps from the same states: the moves
         # applied over the timed steps shift u_old, so the later steps change
         # working sets that the first rotation does not
@@ -778,7 +846,7 @@ def main():
     # (step i: state i % NB, records (i + i // NB) % NB), so each QP's warm
     # start comes from another QP's solution and the active sets move
     harder = None
-    if not args.headline_only:
+    if extras:
         def bind_h(i):
             st_ = states[i % NB]
             ctx.bind_lin(batches[(i + i // NB) % NB].data_ptr())
@@ -816,9 +884,10 @@ def main():
         finally:
             restore()
     # the sections below run on the context's own state buffers
-    ctx.bind_state()
-    ctx.bind_lin(0)
-    ctx.set_state(u_old, du_old, ws)
+    if args.full:
+        ctx.bind_state()
+        ctx.bind_lin(0)
+        ctx.set_state(u_old, du_old, ws)
 
     def warm():
         """Build launches on a resident batch for --settle-seconds, then the
@@ -838,7 +907,7 @@ def main():
     # K = 1 (the build-dominated figure beside the K = 9 headline),
     # this rank, after the headline measurement
     k1 = None
-    if not args.headline_only:
+    if extras:
         try:
             warm()
             for i in range(2):
@@ -866,7 +935,7 @@ def main():
         # (cmpc_produce_lin), then build + K iterations with
         # the first move applied.
     closed = None
-    if not args.headline_only:
+    if extras:
         try:
             from cmpc.synthetic import synthetic_operating_points, synthetic_u_old
             xs, us, ys = synthetic_operating_points(cfg, B, seed=77 + rank, n_distinct=min(B, 2048))
@@ -1023,10 +1092,10 @@ def main():
     # 1 (cent-ser p = 100) as the reference's B = 1 call through the C++
     # adapter, 2, 3 and 5 at their batch sizes; 4 is the `coupled` section
     configs = None
-    if not args.no_configs and not args.headline_only and world == 1:
+    if not args.no_configs and extras and world == 1:
         configs = run_configs(local, args.settle_seconds, args.steps)
     recorded = None
-    if not args.headline_only and world == 1:
+    if extras and world == 1:
         try:
             recorded = recorded_run_changes(local)
         except Exception as e:  # reported, never required
@@ -1065,7 +1134,7 @@ def main():
         return out_c
 
     coupled = coupled_s64 = None
-    if not args.no_coupled and not args.headline_only:
+    if not args.no_coupled and extras:
         common = ("step = build + K x (all-gather + coupled iteration), first move applied; with "
                   "tiles > 1 the scenarios run as that many tiles on their own streams, each tile's "
                   "all-gather overlapping another tile's iteration (cmpc.coupled.CoupledPipeline; "
@@ -1100,10 +1169,13 @@ def main():
     L = ctx.layout
     avg_build_s = build_ms / max(n_build, 1) / 1e3
     f_build = build_flops(cfg, L.naug, L.nd)
-    achieved_tf = B * S * f_build / avg_build_s / 1e12
+    # (no event-stamped build launch: a plain run whose steps ran fused)
+    achieved_tf = B * S * f_build / avg_build_s / 1e12 if n_build else None
     build_kernel = ("cmpc_build_rows_kernel" if ctx.last_build_kernel() == cmpc.CMPC_BUILD_ROWS
                     else "cmpc_build_kernel")
-    traffic, traffic_prov = pmc_traffic(B, build_kernel)
+    traffic, traffic_prov = (pmc_traffic(B, build_kernel) if args.full else
+                             (None, {"file": "profiles/pmc_build_coop_p50.json",
+                                     "status": "not looked up: a --full run does"}))
 
     out = {
         "metric": "QP solves/sec (whole node), cooperative-parallel MPC, horizon p=50",
@@ -1114,6 +1186,7 @@ def main():
         "launch": launch,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": elapsed_max / args.steps * 1e3,
         "rank_ms_per_step": [e / args.steps * 1e3 for e in rank_elapsed],
         "clock_settle": {"seconds": t_settle, "steps": settle_steps,
@@ -1139,7 +1212,7 @@ def main():
             "achieved": achieved_tf,
             "peak": FP64_PEAK_TFLOPS,
             "unit": "TFLOP/s",
-            "frac": achieved_tf / FP64_PEAK_TFLOPS,
+            "frac": achieved_tf / FP64_PEAK_TFLOPS if n_build else None,
             "traffic": traffic,
             "traffic_provenance": traffic_prov,
             "flops_per_qp": f_build,
@@ -1169,7 +1242,7 @@ def main():
                      "FMAs per iteration"),
         },
         "kernels_ms_per_step": {"build": build_ms / max(n_build, 1),
-                                "iterate": iter_ms / max(n_iter, 1),
+                                "iterate": iter_ms / max(n_iter, 1) if args.full else None,
                                 "build_events": args.build_events,
                                 "build_event_stride": ev_stride,
                                 "note": "build: HIP events on every timed step (--build-events timed) or "
@@ -1199,7 +1272,7 @@ def main():
         "coupled": coupled,
         "coupled_s64": coupled_s64,
     }
-    if rank == 0 and world == 1 and not args.no_cpu and not args.headline_only:
+    if rank == 0 and world == 1 and not args.no_cpu and extras:
         try:
             out["cpu_baseline"] = cpu_baseline(cfg, arrays, lin0, u_old, K, args.cpu_seconds)
         except Exception as e:  # the baseline is reported, never required

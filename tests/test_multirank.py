@@ -242,7 +242,7 @@ def test_gpu_bench_force_dist_single_rank():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py",
-           "--gpus", "1", "--force-dist", "--steps", "4", "--warmup", "1", "--no-cpu",
+           "--gpus", "1", "--full", "--force-dist", "--steps", "4", "--warmup", "1", "--no-cpu",
            "--batch", "4096", "--input-batches", "2", "--coupled-batch", "512",
            "--settle-seconds", "0.02"]
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=240)
@@ -264,6 +264,66 @@ def test_gpu_bench_force_dist_single_rank():
     # the recorded run's solver load beside the synthetic one
     assert d["recorded_run_working_set_changes_per_qp_step"] == d["recorded_run"]["working_set_changes_per_qp_step"]
     assert d["recorded_run_working_set_changes_per_qp_step"] < d["working_set_changes_per_qp_step"]
+
+
+@pytest.mark.gpu
+def test_gpu_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    """A plain bench.py run times exactly --steps steps, leaves every --full
+    section out of its line, and --dump-outputs writes the last timed step's
+    outputs as float64 arrays that a second run with the same arguments (and
+    a settle phase of another length) reproduces bit for bit."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = []
+    for tag, settle in (("a", "0.02"), ("b", "0.06")):
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "6", "--warmup", "2", "--batch", "4096",
+               "--input-batches", "2", "--settle-seconds", settle, "--dump-outputs", str(tmp_path / tag)]
+        r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+    for d in lines:
+        assert d["steps"] == 6 and d["warmup"] == 2 and d["full"] is False
+        assert d["value"] > 0 and d["ms_per_step"] > 0 and d["qp_status_ok_fraction"] == 1.0
+        assert abs(d["value"] - 4096 * 2 * 9 / (d["ms_per_step"] * 1e-3)) <= 1e-9 * d["value"]
+        for key in ("k1", "harder_qp", "configs", "closed_loop_device_resident", "coupled", "coupled_s64",
+                    "recorded_run", "working_set_changes_per_step"):
+            assert d[key] is None
+        assert "cpu_baseline" not in d and d["kernels_ms_per_step"]["iterate"] is None
+    assert lines[0]["clock_settle"]["steps"] != lines[1]["clock_settle"]["steps"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["du.npy", "status.npy", "u_old.npy", "working_set.npy", "working_set_changes.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float64 and a.shape[0] == 4096 * 2 and np.isfinite(a).all()
+        assert np.array_equal(a, b), n
+    assert np.abs(np.load(tmp_path / "a" / "du.npy")).max() > 0
+
+
+def test_bench_dump_outputs_samples_large_outputs(tmp_path, monkeypatch):
+    """dump_outputs writes float64; past the size limit it writes the same
+    seeded sample of rows of every array, with their indices."""
+    b = _bench_module()
+    rng = np.random.default_rng(5)
+    arrays = {"du": rng.standard_normal((1000, 4)), "status": np.arange(1000, dtype=np.int32),
+              "ws": np.arange(1000, dtype=np.uint32) * 4000000}
+    b.dump_outputs(str(tmp_path / "all"), 0, 1, arrays)
+    assert sorted(os.listdir(tmp_path / "all")) == ["du.npy", "status.npy", "ws.npy"]
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "all" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, v.astype(np.float64))
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 2 * 100 * 8 * 7)  # 100 rows per rank of two
+    for run in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / run), 1, 2, arrays)
+    rows = np.load(tmp_path / "s1" / "rows.rank1.npy")
+    assert rows.shape == (100,) and len(np.unique(rows)) == 100 and (np.diff(rows) > 0).all()
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "rows.rank1.npy"))
+    idx = rows.astype(np.int64)
+    for k, v in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "s1" / (k + ".rank1.npy")), v[idx].astype(np.float64))
+    total = sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1"))
+    assert total <= 100 * 8 * 7 + 4 * 128
 
 
 def _bench_module():

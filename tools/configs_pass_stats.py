@@ -1,5 +1,5 @@
 """Kernel statistics of the configs section's event-timed passes, cut from a
-rocprofv3 kernel trace of `bench.py --configs-only` (which brackets each
+rocprofv3 kernel trace of `bench.py --full --configs-only` (which brackets each
 config's event-timed pass with torch.cuda._sleep launches), against the event
 times (kernels_ms) of an unprofiled bench line (the profiled run's own events
 are perturbed by the tracer; without a reference line they are used).

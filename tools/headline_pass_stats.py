@@ -1,5 +1,5 @@
 """Kernel statistics of the headline's own launches, cut from a rocprofv3
-kernel trace of `bench.py --headline-only --markers`.
+kernel trace of `bench.py --full --headline-only --markers`.
 
 The bench brackets two passes with torch.cuda._sleep marker launches:
   pass 1: the timed steps (build with events, the iterate without),

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""Copy the rocprofv3 summaries of one GPU round into profiles/ (tracked).
+"""Copy the rocprofv3 summaries of one GPU round (tools/gpu_round.sh TAG) into
+profiles/ (tracked).
 
 usage: python tools/summarize_profiles.py TAG ROUND [BATCH]
 
-  gpurun_out/prof_TAG/run_kernel_stats.csv      -> profiles/ROUND_kernel_stats.csv
-  gpurun_out/cfgprof_TAG/run_kernel_stats.csv   -> profiles/ROUND_configs_kernel_stats.csv
+RUN is the round's output directory ($CMPC_RUN_DIR, default run_out):
+  RUN/prof_TAG/run_kernel_stats.csv      -> profiles/ROUND_kernel_stats.csv
+  RUN/cfgprof_TAG/run_kernel_stats.csv   -> profiles/ROUND_configs_kernel_stats.csv
                                                  (+ that run's configs line)
-  gpurun_out/pmcTAG_{sq1,sq2,fetch,write}/...   -> profiles/ROUND_pmc.json
+  RUN/pmcTAG_{sq1,sq2,fetch,write}/...   -> profiles/ROUND_pmc.json
                                                  + profiles/pmc_build_coop_p50.json
 
 Counters are the median over a kernel's dispatches.  HBM bytes per launch
@@ -23,7 +25,7 @@ import sys
 from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "gpurun_out")
+OUT = os.path.join(ROOT, os.environ.get("CMPC_RUN_DIR", "run_out"))
 PROF = os.path.join(ROOT, "profiles")
 
 
@@ -54,7 +56,7 @@ def main():
         shutil.copy(ks, os.path.join(PROF, f"{rnd}_kernel_stats.csv"))
         print("copied", ks)
     cs = os.path.join(OUT, f"cfgprof_{tag}", "run_kernel_stats.csv")
-    if os.path.exists(cs):  # bench.py --configs-only under rocprofv3 --stats
+    if os.path.exists(cs):  # bench.py --full --configs-only under rocprofv3 --stats
         shutil.copy(cs, os.path.join(PROF, f"{rnd}_configs_kernel_stats.csv"))
         shutil.copy(os.path.join(OUT, f"cfgprof_{tag}.json"), os.path.join(PROF, f"{rnd}_configs_bench.json"))
         print("copied", cs)
