@@ -21,14 +21,14 @@ from ._abi import (CMPC_BUILD_AUTO, CMPC_BUILD_ROWS, CMPC_BUILD_SPLIT, CMPC_BUIL
                    CMPC_APPLY_MOVE, CMPC_KERNEL_BUILD, CMPC_KERNEL_ITERATE,
                    CMPC_KERNEL_PRODUCE, CMPC_KERNEL_OBSERVE_POST, CMPC_KERNEL_OBSERVE_PRIOR, CMPC_QP_INFEASIBLE,
                    CMPC_QP_MAX_NWSR, CMPC_QP_NOT_PD, CMPC_QP_NONFINITE, CMPC_QP_OK, CMPC_TRACE, CmpcDims,
-                   CmpcLayout, bptr, check, dptr, iptr, load_library, uptr)
+                   CmpcLayout, CmpcPlan, CMPC_PLAN_DU_OTHER, bptr, check, dptr, iptr, load_library, uptr)
 from .configs import ControllerConfig, SetupFile, reference_config, reference_observer_gain, reference_setup
 from .problem import ControllerArrays, controller_arrays, plant_input_from_plans
 
 __all__ = ["Context", "ControllerConfig", "SetupFile", "reference_config", "reference_setup",
            "reference_observer_gain", "controller_arrays",
            "plant_input_from_plans", "plant_lin_record", "plant_default", "plant_output",
-           "layout_of", "rows_lds_model", "qp_solve_batch", "CMPC_APPLY_MOVE", "CMPC_TRACE", "CMPC_QP_OK",
+           "layout_of", "plan", "plan_error_string", "rows_lds_model", "qp_solve_batch", "CMPC_APPLY_MOVE", "CMPC_TRACE", "CMPC_QP_OK",
            "CMPC_QP_MAX_NWSR", "CMPC_QP_INFEASIBLE", "CMPC_QP_NOT_PD",
            "CMPC_QP_NONFINITE"]
 
@@ -37,6 +37,23 @@ def layout_of(dims: CmpcDims) -> CmpcLayout:
     L = CmpcLayout()
     check(load_library().cmpc_layout_of(ctypes.byref(dims), ctypes.byref(L)), "cmpc_layout_of")
     return L
+
+
+def plan(dims: CmpcDims, cus: int, build: int = CMPC_BUILD_AUTO, solve: int = CMPC_SOLVE_AUTO,
+         step: int = CMPC_STEP_AUTO, K: int = 1, flags: int = 0) -> CmpcPlan:
+    """Which kernels a batch of dims.B scenarios gets on a device of `cus`
+    compute units under the three variants, for calls with K iterations
+    and `flags` (CMPC_TRACE, CMPC_PLAN_DU_OTHER): cmpc_plan, the library's own
+    selection (csrc/dispatch.cpp), answered without a device."""
+    out = CmpcPlan()
+    check(load_library().cmpc_plan(ctypes.byref(dims), int(cus), int(build), int(solve), int(step), int(K),
+                                   int(flags), ctypes.byref(out)), "cmpc_plan")
+    return out
+
+
+def plan_error_string(code: int) -> str:
+    """The text cmpc_last_error() holds after a call that failed with this plan error."""
+    return load_library().cmpc_plan_error_string(int(code)).decode()
 
 
 def rows_lds_model(dims: CmpcDims):

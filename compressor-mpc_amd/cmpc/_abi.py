@@ -45,6 +45,14 @@ CMPC_STEP_AUTO = 0
 CMPC_STEP_SPLIT = 1
 CMPC_STEP_FUSED = 2
 
+CMPC_PLAN_DU_OTHER = 0x100
+CMPC_PLAN_OK = 0
+CMPC_PLAN_NO_ROWS_BUILD = 1
+CMPC_PLAN_NO_BUILD = 2
+CMPC_PLAN_NO_ROWS_SOLVE = 3
+CMPC_PLAN_NO_SOLVE = 4
+CMPC_PLAN_NO_FUSED_STEP = 5
+
 
 class CmpcDims(ctypes.Structure):
     _fields_ = [("ns", ctypes.c_int32), ("ndist", ctypes.c_int32),
@@ -67,6 +75,19 @@ class CmpcLayout(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in
                 ("nd", "n_delay_states", "naug", "nobs", "ntot", "nV", "nuo", "nVo",
                  "off_A", "off_B", "off_C", "off_f", "off_x", "off_y", "rec_len")]
+
+
+class CmpcPlan(ctypes.Structure):
+    """cmpc_plan_t: what cmpc_build, the solve calls, cmpc_step and
+    cmpc_control_step launch for a batch (include/cmpc.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in
+                ("build_kernel", "build_error", "solve_kernel", "solve_error",
+                 "step_fused", "step_build_kernel", "step_solve_kernel", "step_error",
+                 "control_fused", "control_build_kernel", "control_solve_kernel",
+                 "control_grid", "control_polled")]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 def dptr(a: np.ndarray):
@@ -94,7 +115,7 @@ EXPORTS = (
     "cmpc_layout_of", "cmpc_create", "cmpc_destroy", "cmpc_set_stream",
     "cmpc_last_error", "cmpc_get_layout", "cmpc_set_weights", "cmpc_set_constraints",
     "cmpc_set_reference", "cmpc_set_state", "cmpc_get_state", "cmpc_upload_lin",
-    "cmpc_lin_device", "cmpc_build", "cmpc_set_build_variant", "cmpc_rows_lds_model", "cmpc_last_build_kernel", "cmpc_set_solve_variant", "cmpc_last_solve_kernel", "cmpc_set_step_variant", "cmpc_last_step_fused", "cmpc_init_warmstart", "cmpc_iterate", "cmpc_step",
+    "cmpc_lin_device", "cmpc_build", "cmpc_set_build_variant", "cmpc_rows_lds_model", "cmpc_last_build_kernel", "cmpc_set_solve_variant", "cmpc_last_solve_kernel", "cmpc_set_step_variant", "cmpc_last_step_fused", "cmpc_plan", "cmpc_plan_error_string", "cmpc_init_warmstart", "cmpc_iterate", "cmpc_step",
     "cmpc_synchronize", "cmpc_download", "cmpc_download_qp", "cmpc_download_trace",
     "cmpc_enable_timing", "cmpc_kernel_time", "cmpc_set_timing_stride", "cmpc_plant_dims", "cmpc_plant_default",
     "cmpc_plant_output", "cmpc_plant_lin_record", "cmpc_qp_solve_batch", "cmpc_qp_solve_batch_map", "cmpc_bind_lin",
@@ -161,6 +182,9 @@ def load_library(path: str = LIB_PATH):
         "cmpc_last_solve_kernel": ([c_void], ctypes.c_int),
         "cmpc_set_step_variant": ([c_void, ctypes.c_int], ctypes.c_int),
         "cmpc_last_step_fused": ([c_void], ctypes.c_int),
+        "cmpc_plan": ([P(CmpcDims), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, u32,
+                       P(CmpcPlan)], ctypes.c_int),
+        "cmpc_plan_error_string": ([ctypes.c_int], ctypes.c_char_p),
         "cmpc_rows_lds_model": ([P(CmpcDims), P(dbl), P(dbl), P(ctypes.c_int32)], ctypes.c_int),
         "cmpc_init_warmstart": ([c_void], ctypes.c_int),
         "cmpc_iterate": ([c_void, ctypes.c_int, u32], ctypes.c_int),

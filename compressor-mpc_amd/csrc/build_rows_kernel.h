@@ -46,7 +46,7 @@
 
 #include <algorithm>
 
-#include "cmpc_internal.h"
+#include "dispatch.h"
 #include "rows_blocks.inc"
 #include "lane_solve.h"
 #include "solve_rows.h"
@@ -102,9 +102,7 @@
 #define CMPC_T(i)
 #endif
 
-#ifndef CMPC_FUSED_LANE_SOLVE
-#define CMPC_FUSED_LANE_SOLVE 1  // fused nV = 4 steps solve one QP per lane (0: per 16-lane row)
-#endif
+// (CMPC_FUSED_LANE_SOLVE: kernel_dims.h)
 #ifndef CMPC_ROWS_WPE
 #define CMPC_ROWS_WPE 3  // waves per SIMD the kernel is compiled and launched for
 #endif
@@ -745,7 +743,6 @@ template <int NS, int NY, int NU, int M, int WPG, bool RING, int WPE = CMPC_ROWS
 static int rows_launch(const BuildParams& P, hipStream_t s) {
   auto kern = cmpc_build_rows_kernel<NS, NY, 4, NU, M, 2, WPG, RING, WPE, FUSE>;
   const size_t lds = sizeof(double) * ((size_t)P.rows.lds_block + (size_t)P.rows.per_wave * WPG);
-  if (lds > 160 * 1024) return -1;
   if (lds > 64 * 1024)
     cmpc_allow_lds(reinterpret_cast<const void*>(kern), lds);
   int per_cu = cmpc_blocks_per_cu(kern, 64 * WPG, lds);

@@ -19,7 +19,7 @@
 #include <chrono>
 #include <vector>
 
-#include "cmpc_internal.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -38,30 +38,7 @@ int fail(const std::string& msg) {
   } while (0)
 
 int layout_of(const cmpc_dims* d, cmpc_layout* L) {
-  if (!d || !L) return fail("null argument");
-  if (d->ns < 1 || d->ns > CMPC_MAX_NS || d->nu_tot < 1 || d->nu_tot > CMPC_MAX_INPUTS ||
-      d->nu < 1 || d->nu > d->nu_tot || d->ny < 1 || d->p < 1 || d->m < 1 || d->m > d->p ||
-      d->m * d->nu > CMPC_MAX_NV || d->ndist < 0 || d->S < 1 || d->B < 1)
-    return fail("invalid dimensions");
-  std::memset(L, 0, sizeof *L);
-  for (int i = 0; i < d->nu_tot; ++i) {
-    if (d->delay[i] < 0) return fail("negative delay");
-    if (d->delay[i]) L->nd++;
-    L->n_delay_states += d->delay[i];
-  }
-  L->naug = d->ndist + L->n_delay_states;
-  L->nobs = d->ns + d->ndist;
-  L->ntot = L->nobs + L->n_delay_states;
-  L->nV = d->m * d->nu;
-  L->nuo = d->nu_tot - d->nu;
-  L->nVo = d->m * L->nuo;
-  L->off_A = 0;
-  L->off_B = d->ns * d->ns;
-  L->off_C = L->off_B + d->ns * d->nu_tot;
-  L->off_f = L->off_C + d->ny * L->nobs;
-  L->off_x = L->off_f + d->ns;
-  L->off_y = L->off_x + L->naug;
-  L->rec_len = ((L->off_y + d->ny) + 7) / 8 * 8;
+  if (const char* e = cmpc_layout_error(d, L)) return fail(e);
   return 0;
 }
 
@@ -195,10 +172,17 @@ struct cmpc_ctx {
   int solve_variant = CMPC_SOLVE_AUTO;  // cmpc_set_solve_variant
   int last_solve = 0;                   // kernel launched by the last solve
   int step_variant = CMPC_STEP_AUTO;    // cmpc_set_step_variant
-  int cus = 0;                          // compute units of the device (0: not yet queried)
+  int cus = kCusFallback;               // compute units of the device (cmpc_create)
   std::vector<std::pair<const void*, size_t>> bound_ok;  // (device pointer, bytes) cmpc_bind_* validated before
-  bool lds_layout_ok = false;           // lds_layout holds build_lds_layout(d, L)
-  BuildParams lds_layout{};             // (a function of the dimensions only)
+  // what follows from the dimensions, the batch and the CU count, computed on
+  // first use (the layout searches are host time, and the small-batch kernels
+  // take tens of microseconds): the launch parameters, and the plan per kind
+  // of call under the current variants (plan_of)
+  bool bp_ok = false;
+  BuildParams bp{};                     // cmpc_dispatch_params; bp_error: its error text
+  const char* bp_error = nullptr;
+  cmpc_plan_t plans[8];
+  unsigned plans_valid = 0;             // bit k: plans[k] holds; cleared by cmpc_set_*_variant
   int last_step_fused = 0;
   // timing
   int timing = 0;  // bit k: kernel k (CMPC_KERNEL_*) is timed
@@ -359,9 +343,55 @@ int solve_params(cmpc_ctx* c, SolveParams* P) {
   return 0;
 }
 
+// what follows from the dimensions, the batch and the CU count, once
+void ensure_bp(cmpc_ctx* c) {
+  if (c->bp_ok) return;
+  c->bp_error = cmpc_dispatch_params(c->d, c->L, c->nqp, c->cus, &c->bp);
+  c->bp.co = c->co;
+  c->bp_ok = true;
+}
+
+// the build launch parameters: that part, and the buffers as they are bound now
+int build_params(cmpc_ctx* c, BuildParams& P) {
+  ensure_bp(c);
+  if (c->bp_error) return fail(c->bp_error);
+  P = c->bp;
+  P.lin = c->lin_bound ? c->lin_bound : c->lin;
+  P.cfg = c->cfg;
+  P.u_old = c->u_old;
+  P.qp = c->qp;
+  return 0;
+}
+
+// The plan (cmpc_dispatch_plan) for a call with K iterations: which kernel
+// each entry point launches.  Derived once per kind of call and variant
+// setting, so a step pays no selection work.  (With bp_error no build kernel
+// is available, and the build calls report that error first.)
+const cmpc_plan_t& plan_of(cmpc_ctx* c, int K, bool trace, bool du_other) {
+  const unsigned k = (K > 0 ? 1u : 0u) | (trace ? 2u : 0u) | (du_other ? 4u : 0u);
+  if (!((c->plans_valid >> k) & 1)) {
+    ensure_bp(c);
+    c->plans[k] = cmpc_dispatch_plan(c->d, c->L, c->bp, c->build_variant, c->solve_variant, c->step_variant,
+                                     K > 0 ? 1 : 0, trace, du_other);
+    c->plans_valid |= 1u << k;
+  }
+  return c->plans[k];
+}
+
+int plan_mismatch(const char* what) {
+  return fail(std::string("internal error: plan and launcher disagree (") + what + ")");
+}
+
 }  // namespace
 
 extern "C" {
+
+int cmpc_plan(const cmpc_dims* dims, int cus, int build_variant, int solve_variant, int step_variant, int K,
+              uint32_t flags, cmpc_plan_t* plan) {
+  if (const char* e = cmpc_plan_or_error(dims, cus, build_variant, solve_variant, step_variant, K, flags, plan))
+    return fail(e);
+  return 0;
+}
 
 int cmpc_layout_of(const cmpc_dims* d, cmpc_layout* L) { return layout_of(d, L); }
 
@@ -373,29 +403,8 @@ int cmpc_create(cmpc_ctx** out, const cmpc_dims* dims, int device) {
   cmpc_layout L;
   if (layout_of(dims, &L)) return -1;
   const cmpc_dims& d = *dims;
-  if (64 % d.S != 0) return fail("S must divide the wavefront size (64)");
-  // S sub-controllers share the inputs (nu_tot = S nu), or S = 1 with
-  // nu < nu_tot: one stand-alone sub-controller whose other controllers'
-  // plans come with every cmpc_get_input (DistributedController::GetInput)
-  if (L.nuo != (d.S - 1) * d.nu && d.S != 1)
-    return fail("nu_tot must equal S * nu (each sub-controller owns nu inputs), or S = 1");
-  if (L.nd > CMPC_ND_MAX) return fail("more than 4 delayed inputs");
-  // A one-step delay with several delayed inputs: the reference's BComposite
-  // (libs/aug_lin_sys.cc:189-197) places such an input at index
-  // n_delayed_inputs + (sum of the earlier blocks' D - 1) - 1 of the
-  // augmented state, which is another input's delay state (only a single
-  // delayed input gets its own slot).  That mapping is not reproduced.
-  for (int i = 0; i < d.nu_tot; ++i)
-    if (d.delay[i] == 1 && L.nd > 1)
-      return fail("a delay of one step with several delayed inputs: the reference's BComposite "
-                  "maps it onto another input's delay state (aug_lin_sys.cc:189-197); not supported");
-  if (d.ns + d.nu_tot > 15) return fail("ns + nu_tot must be <= 15 (16-lane DPP rows)");
-  if (d.m * d.nu_tot + 1 > 16) return fail("m * nu_tot + 1 must be <= 16 (gather lanes of a DPP row)");
-  if (d.ny > 4) return fail("ny > 4 is not instantiated in the build kernel (one DPP row per output)");
-  if (d.ns + d.ny + L.nd > 16)
-    return fail("ns + ny + (delayed inputs) must be <= 16 (free-response DPP row)");
+  if (const char* e = cmpc_context_dims_error(d, L)) return fail(e);
   const long long nqp = (long long)d.B * d.S;
-  if (nqp > (1LL << 30)) return fail("batch too large");
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail("no such HIP device");
@@ -404,7 +413,7 @@ int cmpc_create(cmpc_ctx** out, const cmpc_dims* dims, int device) {
   c->L = L;
   c->device = device;
   c->nqp = (int)nqp;
-  c->qp_len = (L.nV * L.nV + L.nV + L.nV * L.nVo + 1) / 2 * 2;
+  c->qp_len = cmpc_qp_len(L);
   int off = 0;
   c->co.lwt = off; off += d.ny * d.ny;
   c->co.yhat = off; off += d.p * d.ny;
@@ -432,6 +441,8 @@ int cmpc_create(cmpc_ctx** out, const cmpc_dims* dims, int device) {
   if (hipSetDevice(device) != hipSuccess) return cleanup(fail("hipSetDevice failed"));
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
     return cleanup(fail("hipStreamCreate failed"));
+  if (hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || c->cus < 1)
+    c->cus = kCusFallback;
   c->own_stream = true;
   const size_t n = (size_t)c->nqp;
   if (hipMalloc(&c->lin, sizeof(double) * n * L.rec_len) != hipSuccess ||
@@ -939,11 +950,9 @@ int cmpc_observe_apply(cmpc_ctx* c) {
   return tl.end();
 }
 
-static int build_params(cmpc_ctx* c, BuildParams& P);
-
 // NerveCenter::GetNextInput on the device: cmpc_observe_step + cmpc_step(K,
-// 0) + cmpc_observe_apply, as one kernel where the batch takes the
-// one-QP-per-wave fused step (cmpc_control_step_kernel), else the three calls.
+// 0) + cmpc_observe_apply, as one kernel (cmpc_control_step_kernel) where
+// the plan says so, else the three calls.
 static int control_step(cmpc_ctx* c, const double* u_full, const double* y, int K, bool* flagged);
 
 int cmpc_control_step(cmpc_ctx* c, const double* u_full, const double* y, int K) {
@@ -960,54 +969,38 @@ static int control_step(cmpc_ctx* c, const double* u_full, const double* y, int 
   if (c->obs_plant < 0) return fail("cmpc_control_step: call cmpc_observer_init first");
   HIP_TRY(hipSetDevice(c->device));
   if (observer_upload_M(c)) return -1;
-  if (!c->cus) (void)hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, c->device);
-  const cmpc_dims& d = c->d;
-  // one launch up to four QPs per CU: it wins there (config 5's cent-par
-  // p = 200 at 1 024 QPs 50.7 vs 58.6 us, coop-par p = 50 at 512 QPs 48.5 vs
-  // 49.5 us) and loses above (2 048 QPs: 75.2 vs 72.7 and 102.0 vs 73.0 us;
-  // tools/control_step_ab.py, profiles/r6r_control_step_ab.txt)
-  const bool fuse = K > 0 && c->step_variant != CMPC_STEP_SPLIT && c->build_variant == CMPC_BUILD_AUTO &&
-                    c->solve_variant == CMPC_SOLVE_AUTO && c->nqp <= 4 * std::max(c->cus, 1) &&
-                    c->L.nuo == (d.S - 1) * d.nu;
-  if (fuse) {
-    if (ensure_cfg(c)) return -1;
-    ControlStepParams C;
-    std::memset(&C, 0, sizeof C);
-    if (observer_produce_params(c, u_full, y, true, C.pr)) return -1;
-    c->lin_bound = nullptr;  // the build reads the produced records
-    if (build_params(c, C.b)) return -1;
-    // up to one QP per CU the build runs as role-split pairs, two QP slots
-    // per workgroup (cent-ser B = 1 build 17.7 -> 15.7 us, §3.1)
-#ifndef CMPC_CONTROL_SPLIT
-#define CMPC_CONTROL_SPLIT 1
-#endif
-    C.b.split = CMPC_CONTROL_SPLIT && c->nqp <= std::max(c->cus, 1);
-    if (C.b.split) C.b.grid = std::max(1, (c->nqp + 1) / 2);
-    solve_params(c, &C.b.sv);
-    C.b.sv.K = K;
-    C.b.sv.flags = 0;  // u_old += du is the a-priori phase's
-    observer_params(c, &C.ob);
-    C.pr_off = ((C.pr.S * C.pr.rec_len + C.pr.naug + 3) / 4) * 2;  // doubles, 16-byte aligned
-    const bool flag = flagged && c->done_dev && C.b.grid == 1;
-    C.done = flag ? c->done_dev : nullptr;
-    C.seq = flag ? ++c->done_seq : 0u;
-    TimedLaunch tl(c, CMPC_KERNEL_STEP);
-    if (tl.begin()) return -1;
-    int solver = 0;
-    if (cmpc_launch_control_step(C, d.ns, d.ny, d.nu, d.m, c->stream, &solver) == 0) {
-      if (check_launch("control step kernel")) return -1;
-      c->last_build = C.b.split ? CMPC_BUILD_SPLIT : CMPC_BUILD_WAVE;
-      c->last_solve = solver;
-      c->last_step_fused = 1;
-      c->obs_steps++;  // the delay-block rings advance by one (cmpc_observe_apply)
-      if (flagged) *flagged = flag;
-      return tl.end();
-    }
-    cmpc_launch_events = LaunchEvents{};
+  const cmpc_plan_t& pl = plan_of(c, K, false, false);
+  if (!pl.control_fused) {
+    if (cmpc_observe_step(c, u_full, y)) return -1;
+    if (cmpc_step(c, K, 0)) return -1;
+    return cmpc_observe_apply(c);
   }
-  if (cmpc_observe_step(c, u_full, y)) return -1;
-  if (cmpc_step(c, K, 0)) return -1;
-  return cmpc_observe_apply(c);
+  if (ensure_cfg(c)) return -1;
+  ControlStepParams C;
+  std::memset(&C, 0, sizeof C);
+  if (observer_produce_params(c, u_full, y, true, C.pr)) return -1;
+  c->lin_bound = nullptr;  // the build reads the produced records
+  if (build_params(c, C.b)) return -1;
+  C.b.split = pl.control_build_kernel == CMPC_BUILD_SPLIT;
+  C.b.grid = pl.control_grid;
+  solve_params(c, &C.b.sv);
+  C.b.sv.K = K;
+  C.b.sv.flags = 0;  // u_old += du is the a-priori phase's
+  observer_params(c, &C.ob);
+  C.pr_off = cmpc_control_pr_off(C.pr.S, C.pr.rec_len, C.pr.naug);
+  const bool flag = flagged && c->done_dev && pl.control_polled;
+  C.done = flag ? c->done_dev : nullptr;
+  C.seq = flag ? ++c->done_seq : 0u;
+  TimedLaunch tl(c, CMPC_KERNEL_STEP);
+  if (tl.begin()) return -1;
+  if (cmpc_launch_control_step(C, c->d, c->stream)) return plan_mismatch("control step");
+  if (check_launch("control step kernel")) return -1;
+  c->last_build = pl.control_build_kernel;
+  c->last_solve = pl.control_solve_kernel;
+  c->last_step_fused = 1;
+  c->obs_steps++;  // the delay-block rings advance by one (cmpc_observe_apply)
+  if (flagged) *flagged = flag;
+  return tl.end();
 }
 
 // copies host arrays (nullptr entries skipped) into the context's staging
@@ -1504,89 +1497,13 @@ int cmpc_set_observer_state(cmpc_ctx* c, const double* host) {
   return 0;
 }
 
-// LDS layout of the build kernel (doubles; must match cmpc_kernels.hip).
-// Bank model (MI355X_MICROARCH.md §LDS): ds_read_b64 is serviced per 32-lane
-// group with 32 double-wide banks, ds_write_b64 per 16-lane group with 16.
-// Per step the gather lanes of rows 0/1 (one read group) read lines at
-// line_off[c] + (m-1-k) + r - D_c and row o's Markov lanes write at
-// line_off[c] + m - 1 + r.  Lines (length m - 1 + p) are placed so that input
-// c's read window sits at residues [m*pi(c), m*pi(c) + m) mod 32 and the
-// write residues are distinct mod 16; rows are 16 mod 32 apart so row 1's
-// window is disjoint from row 0's.  All addresses advance together, so a
-// layout that is conflict-free at one step is conflict-free at every step.
-static void build_lds_layout(const cmpc_dims& d, const cmpc_layout& L, BuildParams* P) {
-  const int nut = d.nu_tot, M = d.m, ng = M * nut + 1;
-  auto up = [](int v, int a) { return (v + a - 1) / a * a; };
-  auto place = [&](const int* perm, int* off) {  // returns total length
-    int cur = 0;
-    for (int c = 0; c < nut; ++c) {
-      const int want = (((M * perm[c] + d.delay[c]) % 32) + 32) % 32;
-      int o = cur;
-      while (((o % 32) + 32) % 32 != want) ++o;
-      off[c] = o;
-      cur = o + M - 1 + d.p;
-    }
-    return cur;
-  };
-  int perm[CMPC_MAX_INPUTS], best[CMPC_MAX_INPUTS], off[CMPC_MAX_INPUTS];
-  for (int c = 0; c < nut; ++c) perm[c] = best[c] = c;
-  int best_len = -1;
-  do {  // permutations of the read windows: first one whose writes are conflict-free
-    const int len = place(perm, off);
-    bool ok = true;
-    for (int a = 0; a < nut && ok; ++a)
-      for (int b = a + 1; b < nut && ok; ++b)
-        ok = (off[a] - off[b]) % 16 != 0;
-    if (ok && (best_len < 0 || len < best_len)) {
-      best_len = len;
-      for (int c = 0; c < nut; ++c) best[c] = perm[c];
-    }
-  } while (std::next_permutation(perm, perm + nut));
-  const int len = place(best, off);
-  for (int c = 0; c < nut; ++c) P->line_off[c] = off[c];
-  int rs = up(len, 2);
-  while (rs % 32 != 16) rs += 2;
-  P->line_rs = rs;
-  const int head = L.rec_len + 8 + d.ny * L.nobs + 4;  // record, u_old, C_hat, kappa
-  int o = std::max(std::max(d.ny * rs, (d.ny - 1) * ng * L.nV), head);
-  o = up(o, 32) + 16;                                   // w table at 16 mod 32
-  P->w_off = o;
-  o += up((d.p + 3) * d.ny, 2);
-  while (o % 32 != (M * nut) % 32) o += 2;               // z slots next to row 0's window
-  P->zs_off = o;
-  if (d.ny == 4) {
-    // pre-pass z lines: stride = 1 mod 32, so row o's z read sits at residue
-    // m*nu_tot + o (between the line windows of rows o and o+1 at 0 / 16 mod 32)
-    // and the four writes of a step hit distinct banks
-    int zst = d.p;
-    while (zst % 32 != 1) ++zst;
-    P->zl_stride = zst;
-    o += d.ny * zst;
-  } else {
-    P->zl_stride = 4;
-    o += d.ny * 4;
-  }
-  P->lds_per_wave = up(o, 32);
-  P->yl_stride = up((d.p + 1) * d.ny, 32);
-  P->lds_block = up(d.S * P->yl_stride + d.S * d.ny * d.ny + d.S * d.nu * d.nu + 16, 32);
-  // loop segments: the distinct delays inside the horizon, ascending
-  P->nbound = 0;
-  for (int c = 0; c < nut; ++c) {
-    const int D = d.delay[c];
-    if (D <= 0 || D >= d.p) continue;
-    bool seen = false;
-    for (int i = 0; i < P->nbound; ++i) seen = seen || P->bound[i] == D;
-    if (!seen) P->bound[P->nbound++] = D;
-  }
-  std::sort(P->bound, P->bound + P->nbound);
-}
-
 int cmpc_set_build_variant(cmpc_ctx* c, int variant) {
   if (!c) return fail("null context");
   if (variant != CMPC_BUILD_AUTO && variant != CMPC_BUILD_WAVE && variant != CMPC_BUILD_ROWS &&
       variant != CMPC_BUILD_SPLIT)
     return fail("cmpc_set_build_variant: unknown variant");
   c->build_variant = variant;
+  c->plans_valid = 0;
   return 0;
 }
 
@@ -1595,111 +1512,23 @@ int cmpc_last_build_kernel(cmpc_ctx* c) {
   return c->last_build;
 }
 
-static int build_params(cmpc_ctx* c, BuildParams& P);
-
 int cmpc_build(cmpc_ctx* c) {
   if (!c) return fail("null context");
   if (ensure_cfg(c)) return -1;
   HIP_TRY(hipSetDevice(c->device));
-  const cmpc_dims& d = c->d;
   BuildParams P;
   if (build_params(c, P)) return -1;
+  const cmpc_plan_t& pl = plan_of(c, 0, false, false);
+  if (pl.build_error) return fail(cmpc_plan_error_string(pl.build_error));
   TimedLaunch tl(c, CMPC_KERNEL_BUILD);
   if (tl.begin()) return -1;
-  int rc = -1;
-  // AUTO: the row kernel wherever its LDS fits (measured as fast or faster
-  // than the one-QP-per-wave kernel for every plant/controller type at
-  // p = 20, 50, 100, 200: tools/gpu_build_table.sh) and the
-  // batch gives it at least one wave per SIMD; else
-  // the one-QP-per-wave kernel, which has four times the waves for a small
-  // batch (cent p = 200, 1 024 QPs: 0.026 vs 0.057 ms)
-  // Below one QP per SIMD the role-split kernel: two waves per QP
-  // (config 5: 28.1 -> 22.6 us, profiles/r5g_build_split_ab.txt).
-  const bool rows_fill = (c->nqp + 3) / 4 >= 4 * P.cus;
-  const bool split_fit = c->nqp <= 4 * P.cus;
-  if (c->build_variant == CMPC_BUILD_ROWS || (c->build_variant == CMPC_BUILD_AUTO && rows_fill))
-    rc = cmpc_launch_build_rows(P, d.ns, d.ny, d.nu, d.m, c->stream);
-  if (rc && c->build_variant == CMPC_BUILD_ROWS)
-    return fail("row-layout build kernel not available for these dimensions");
-  c->last_build = CMPC_BUILD_ROWS;
-  if (rc) {
-    P.split = c->build_variant == CMPC_BUILD_SPLIT || (c->build_variant == CMPC_BUILD_AUTO && split_fit);
-    if (cmpc_launch_build(P, d.ns, d.ny, d.nu, d.m, c->stream))
-      return fail("build kernel not instantiated for these dimensions (ns, ny, nu, m)");
-    c->last_build = P.split ? CMPC_BUILD_SPLIT : CMPC_BUILD_WAVE;
-  }
+  P.split = pl.build_kernel == CMPC_BUILD_SPLIT;
+  if (pl.build_kernel == CMPC_BUILD_ROWS ? cmpc_launch_build_rows(P, c->d, c->stream)
+                                         : cmpc_launch_build(P, c->d, c->stream))
+    return plan_mismatch("build");
   if (check_launch("build kernel")) return -1;
+  c->last_build = pl.build_kernel;
   return tl.end();
-}
-
-static int build_params(cmpc_ctx* c, BuildParams& P) {
-  const cmpc_dims& d = c->d;
-  const cmpc_layout& L = c->L;
-  std::memset(&P, 0, sizeof P);
-  P.lin = c->lin_bound ? c->lin_bound : c->lin;
-  P.cfg = c->cfg;
-  P.u_old = c->u_old;
-  P.qp = c->qp;
-  P.nqp = c->nqp;
-  P.S = d.S;
-  P.p = d.p;
-  P.nu_tot = d.nu_tot;
-  P.ndist = d.ndist;
-  P.nd = L.nd;
-  P.rec_len = L.rec_len;
-  P.qp_len = c->qp_len;
-  P.off_A = L.off_A; P.off_B = L.off_B; P.off_C = L.off_C;
-  P.off_f = L.off_f; P.off_x = L.off_x; P.off_y = L.off_y;
-  P.nobs = L.nobs;
-  P.co = c->co;
-  int kd = 0, boff = d.ndist + L.nd, dmax = 1;
-  for (int i = 0; i < d.nu_tot; ++i) {
-    P.delay[i] = d.delay[i];
-    P.dindex[i] = -1;
-    if (d.delay[i] > 0) {
-      P.dindex[i] = kd;
-      P.dinput[kd] = i;
-      P.dlen[kd] = d.delay[i];
-      P.boff[kd] = boff;
-      boff += d.delay[i] - 1;
-      dmax = std::max(dmax, d.delay[i]);
-      ++kd;
-    }
-  }
-  P.dmax = dmax;
-  // the LDS layout and the device's CU count are fixed per context: computed
-  // once (the layout search and the attribute query are host time on every
-  // launch of a small batch, whose kernels take tens of microseconds)
-  if (!c->lds_layout_ok) {
-    build_lds_layout(d, L, &c->lds_layout);
-    c->lds_layout_ok = true;
-  }
-  {
-    const BuildParams& T = c->lds_layout;
-    P.lds_block = T.lds_block;
-    P.yl_stride = T.yl_stride;
-    P.lds_per_wave = T.lds_per_wave;
-    std::memcpy(P.line_off, T.line_off, sizeof P.line_off);
-    P.line_rs = T.line_rs;
-    P.w_off = T.w_off;
-    P.zs_off = T.zs_off;
-    P.zl_stride = T.zl_stride;
-    P.nbound = T.nbound;
-    std::memcpy(P.bound, T.bound, sizeof P.bound);
-  }
-  if (L.rec_len > 2 * 64 * CMPC_REC_CHUNKS) return fail("lin record too long for the build kernel");
-  const size_t lds_bytes = sizeof(double) * ((size_t)P.lds_block + (size_t)P.lds_per_wave * CMPC_BUILD_WAVES);
-  if (lds_bytes > 160 * 1024) return fail("horizon/delays too long for the build kernel's LDS");
-  {
-    // persistent grid: the launcher caps this at (resident workgroups per CU,
-    // from the occupancy query: registers and LDS) x CUs, so no workgroup
-    // waits for a second round
-    if (!c->cus) (void)hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, c->device);
-    P.cus = c->cus > 0 ? c->cus : 256;
-    P.grid = std::max(1, (c->nqp + CMPC_BUILD_WAVES - 1) / CMPC_BUILD_WAVES);
-  }
-  cmpc_rows_layout(d, L.nd, L.nobs, L.rec_len, &P.rows);  // cached per dimension set
-  return 0;
 }
 
 // working-set trace buffers for K iterations of every QP (CMPC_TRACE)
@@ -1723,6 +1552,7 @@ int cmpc_set_solve_variant(cmpc_ctx* c, int variant) {
   if (variant != CMPC_SOLVE_AUTO && variant != CMPC_SOLVE_LANE && variant != CMPC_SOLVE_ROWS)
     return fail("cmpc_set_solve_variant: unknown variant");
   c->solve_variant = variant;
+  c->plans_valid = 0;
   return 0;
 }
 
@@ -1731,29 +1561,21 @@ int cmpc_last_solve_kernel(cmpc_ctx* c) {
   return c->last_solve;
 }
 
-// the iterate / init / get-input launch through the selected solve kernel
-static int launch_solve(cmpc_ctx* c, const SolveParams& P, const char* who) {
+// the solve kernel of the plan for this call, or its error; launch_solve
+// launches it (after TimedLaunch::begin, so nothing there may fail over)
+static int solve_kernel_of(cmpc_ctx* c, const SolveParams& P, const char* who, int* kernel) {
+  const cmpc_plan_t& pl = plan_of(c, P.K, P.trace != nullptr, P.du_other != nullptr);
+  if (pl.solve_error) return fail(std::string(who) + ": " + cmpc_plan_error_string(pl.solve_error));
+  *kernel = pl.solve_kernel;
+  return 0;
+}
+
+static int launch_solve(cmpc_ctx* c, const SolveParams& P, int kernel) {
   const int nV = c->L.nV, nu = c->d.nu, nVo = c->L.nVo;
-  // AUTO: the row kernel for small batches of nV >= 6 QPs (centralized: the
-  // lane kernel's nV = 8 solve is one long dependency chain per lane, 17 us
-  // for one solve of 1 024 QPs against 9 us in rows, tools/time_small.py);
-  // at nV = 4 up to four QPs per SIMD (K = 9: 7.7-7.8 vs 9.7-9.9 us from 2
-  // to 1 024 QPs, profiles/r5k_small_batch.txt; in the bench's step loop
-  // with the move applied 9.6-10.2 vs 11.6-12.1 us at 2 048 and 4 096 QPs,
-  // p = 20, profiles/r6r_solver_variant_sweep.txt), the lane kernel above
-  // (8 192 QPs: 11.9 vs 17.5 us)
-  if (!c->cus) (void)hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, c->device);
-  const bool rows_small = nV >= 6 ? c->nqp < CMPC_SOLVE_ROWS_MAX_QP : c->nqp <= 16 * std::max(c->cus, 1);
-  const bool want_rows = c->solve_variant == CMPC_SOLVE_ROWS || (c->solve_variant == CMPC_SOLVE_AUTO && rows_small);
-  if (want_rows && cmpc_launch_solve_rows(P, nV, nu, nVo, c->stream) == 0) {
-    c->last_solve = CMPC_SOLVE_ROWS;
-    return 0;
-  }
-  if (c->solve_variant == CMPC_SOLVE_ROWS)
-    return fail(std::string(who) + ": row solve kernel not available for these dimensions (S must divide 4)");
-  if (cmpc_launch_solve(P, nV, nu, nVo, c->stream))
-    return fail(std::string(who) + ": solve kernel not instantiated for these dimensions");
-  c->last_solve = CMPC_SOLVE_LANE;
+  if (kernel == CMPC_SOLVE_ROWS ? cmpc_launch_solve_rows(P, nV, nu, nVo, c->stream)
+                                : cmpc_launch_solve(P, nV, nu, nVo, c->stream))
+    return plan_mismatch("solve");
+  c->last_solve = kernel;
   return 0;
 }
 
@@ -1764,8 +1586,9 @@ int cmpc_init_warmstart(cmpc_ctx* c) {
   SolveParams P;
   solve_params(c, &P);
   P.init = 1;
-  cmpc_launch_events = LaunchEvents{};  // untimed (a failed timed launch may have left them set)
-  if (launch_solve(c, P, "cmpc_init_warmstart")) return -1;
+  int kernel = 0;
+  if (solve_kernel_of(c, P, "cmpc_init_warmstart", &kernel)) return -1;
+  if (launch_solve(c, P, kernel)) return -1;
   return check_launch("init kernel");
 }
 
@@ -1786,9 +1609,11 @@ int cmpc_iterate(cmpc_ctx* c, int K, uint32_t flags) {
     P.trace = c->trace;
     P.ntrace = c->ntrace;
   }
+  int kernel = 0;
+  if (solve_kernel_of(c, P, "cmpc_iterate", &kernel)) return -1;
   TimedLaunch tl(c, CMPC_KERNEL_ITERATE);
   if (tl.begin()) return -1;
-  if (launch_solve(c, P, "cmpc_iterate")) return -1;
+  if (launch_solve(c, P, kernel)) return -1;
   if (check_launch("iterate kernel")) return -1;
   return tl.end();
 }
@@ -1807,9 +1632,11 @@ int cmpc_get_input(cmpc_ctx* c, const double* du_last, uint32_t flags) {
   P.K = 1;
   P.flags = flags;
   P.du_other = du_last;
+  int kernel = 0;
+  if (solve_kernel_of(c, P, "cmpc_get_input", &kernel)) return -1;
   TimedLaunch tl(c, CMPC_KERNEL_ITERATE);
   if (tl.begin()) return -1;
-  if (launch_solve(c, P, "cmpc_get_input")) return -1;
+  if (launch_solve(c, P, kernel)) return -1;
   if (check_launch("get-input kernel")) return -1;
   return tl.end();
 }
@@ -1927,6 +1754,7 @@ int cmpc_set_step_variant(cmpc_ctx* c, int variant) {
   if (variant != CMPC_STEP_AUTO && variant != CMPC_STEP_SPLIT && variant != CMPC_STEP_FUSED)
     return fail("cmpc_set_step_variant: unknown variant");
   c->step_variant = variant;
+  c->plans_valid = 0;
   return 0;
 }
 
@@ -1936,79 +1764,42 @@ int cmpc_last_step_fused(cmpc_ctx* c) {
 }
 
 // GetNextInputWithTiming's device part: the build, then K Jacobi iterations.
-// On small batches one fused launch (the build kernel solves its own QPs:
-// no launch gap, no HBM round trip of H, f, G); else cmpc_build + cmpc_iterate.
+// One fused launch where the plan says so (the build kernel solves its own
+// QPs: no launch gap, no HBM round trip of H, f, G); else cmpc_build +
+// cmpc_iterate.
 int cmpc_step(cmpc_ctx* c, int K, uint32_t flags) {
   if (!c) return fail("null context");
   if (K < 0) return fail("K must be >= 0");
-  // AUTO fuses small batches on the build kernel AUTO would pick anyway: the
-  // one-QP-per-wave kernel under one row group per SIMD (its own row solver
-  // for centralized QPs, SURVEY config 5: 40.1 vs 44.8 us per step; the lane
-  // solver of wave 0 after a workgroup barrier for S = 2, 4), the row kernel
-  // from one row group per SIMD up to 16 384 QPs (config 2)
-  if (!c->cus) (void)hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, c->device);
-  // (AUTO fuses nV >= 6 steps from one to four QPs per CU at p >= 50 only:
-  // below one per CU the role-split build and the iterate kernel are faster
-  // (cent-ser B = 1 21.8 vs 24.4 us); in that range fused wins by 2-3 %
-  // (config 5: 37.3 vs 38.1 us with the move; ser-cent p = 100 512 QPs 37.6
-  // vs 38.4 us) but loses at p = 20 (15.0 vs 13.9 us), and above it the split
-  // steps win: 2 048 QPs 17.1 vs 28.3 us (par-cent p = 20) and 60.1 vs 73.0 us
-  // (ser-cent p = 100), 8 192 QPs 112 vs 135 us (par-cent p = 200)
-  // (tools/step_variant_ab.py, profiles/r6r_step_variant_sweep.txt; it costs
-  // 3 % at 4 096 QPs for p = 50 and 200).  nV = 4 steps are two launches at
-  // every size (coop-par 1 024 QPs 17.8 vs 18.6 us, config 2 26.4 vs
-  // 54.1 us; profiles/r5j_split_step_ab.txt, profiles/r5k_small_batch.txt))
-  const int cus1 = std::max(c->cus, 1);
-  const bool auto_fuse = c->L.nV >= 6 && c->nqp > cus1 && c->nqp <= 4 * cus1 && c->d.p >= 50;
-  const bool want = c->step_variant == CMPC_STEP_FUSED ||
-                    (c->step_variant == CMPC_STEP_AUTO && auto_fuse &&
-                     c->build_variant == CMPC_BUILD_AUTO && c->solve_variant == CMPC_SOLVE_AUTO);
-  if (want && K > 0 && c->L.nuo == (c->d.S - 1) * c->d.nu) {
-    if (ensure_cfg(c)) return -1;
-    HIP_TRY(hipSetDevice(c->device));
-    BuildParams P;
-    if (build_params(c, P)) return -1;
-    solve_params(c, &P.sv);
-    P.sv.K = K;
-    P.sv.flags = flags;
-    if ((flags & CMPC_TRACE) && trace_buffers(c, K)) return -1;
-    if (flags & CMPC_TRACE) {
-      P.sv.trace = c->trace;
-      P.sv.ntrace = c->ntrace;
-    }
-    TimedLaunch tl(c, CMPC_KERNEL_STEP);
-    if (tl.begin()) return -1;
-    const cmpc_dims& d = c->d;
-    // the build kernel AUTO would pick: one QP per wave below one row group per
-    // SIMD, else four QPs per wave
-    const bool rows_fill = (c->nqp + 3) / 4 >= 4 * P.cus;
-    int rc = -1, kind = CMPC_BUILD_ROWS, solver = CMPC_SOLVE_ROWS;
-    if (!rows_fill) {
-      rc = cmpc_launch_step_wave(P, d.ns, d.ny, d.nu, d.m, c->stream, &solver);
-      kind = CMPC_BUILD_WAVE;
-    }
-    // AUTO leaves the row kernel's fused step with the lane solver (nV <= 4)
-    // to the two launches, measured faster on every box this round (config 2:
-    // 32.0-32.2 vs 33.7-33.9 us back to back, profiles/r4i_small_batch.txt)
-    const bool rows_lane = c->L.nV <= 4 && c->step_variant == CMPC_STEP_AUTO;
-    if (rc && !(rows_fill && rows_lane)) {
-      rc = cmpc_launch_step_rows(P, d.ns, d.ny, d.nu, d.m, c->stream, &solver);
-      kind = CMPC_BUILD_ROWS;
-    }
-    if (rc == 0) {
-      if (check_launch("fused step kernel")) return -1;
-      c->last_build = kind;
-      c->last_solve = solver;
-      c->last_step_fused = 1;
-      return tl.end();
-    }
-    cmpc_launch_events = LaunchEvents{};
-    if (c->step_variant == CMPC_STEP_FUSED)
-      return fail("cmpc_step: no fused step kernel for these dimensions");
+  const bool trace = (flags & CMPC_TRACE) != 0;
+  const cmpc_plan_t& pl = plan_of(c, K, trace, false);
+  if (!pl.step_fused && !pl.step_error) {
+    c->last_step_fused = 0;
+    if (cmpc_build(c)) return -1;
+    return cmpc_iterate(c, K, flags);
   }
-  c->last_step_fused = 0;
-  if (cmpc_build(c)) return -1;
-  return cmpc_iterate(c, K, flags);
+  if (ensure_cfg(c)) return -1;
+  HIP_TRY(hipSetDevice(c->device));
+  BuildParams P;
+  if (build_params(c, P)) return -1;
+  if (pl.step_error) return fail(cmpc_plan_error_string(pl.step_error));
+  solve_params(c, &P.sv);
+  P.sv.K = K;
+  P.sv.flags = flags;
+  if (trace) {
+    if (trace_buffers(c, K)) return -1;
+    P.sv.trace = c->trace;
+    P.sv.ntrace = c->ntrace;
+  }
+  TimedLaunch tl(c, CMPC_KERNEL_STEP);
+  if (tl.begin()) return -1;
+  if (pl.step_build_kernel == CMPC_BUILD_ROWS ? cmpc_launch_step_rows(P, c->d, pl.step_solve_kernel, c->stream)
+                                              : cmpc_launch_step_wave(P, c->d, c->stream))
+    return plan_mismatch("fused step");
+  if (check_launch("fused step kernel")) return -1;
+  c->last_build = pl.step_build_kernel;
+  c->last_solve = pl.step_solve_kernel;
+  c->last_step_fused = 1;
+  return tl.end();
 }
 
 int cmpc_synchronize(cmpc_ctx* c) {

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/cmpc.h"
+#include "kernel_dims.h"
 
 // Kernel timing (cmpc_enable_timing).  cmpc_abi.cpp sets these events around
 // a timed launch (null otherwise); the launchers hand them to
@@ -176,7 +177,7 @@ struct BuildParams {
   int nbound;                    // distinct delays 0 < D < p, ascending (loop segments)
   int bound[CMPC_MAX_INPUTS];
   int grid;                      // workgroups needed (one QP per wave); launcher caps it
-  int split;                     // cmpc_launch_build: the role-split kernel (ny <= 3)
+  int split;                     // cmpc_launch_build: the role-split kernel (every ny)
   int cus;                       // compute units of the device
   RowsLayout rows;               // row-layout kernel (four QPs per wave)
   // fused step (cmpc_step on small batches): the K Jacobi iterations run in
@@ -270,8 +271,7 @@ struct ControlStepParams {
   uint32_t* done;
   uint32_t seq;
 };
-int cmpc_launch_control_step(const ControlStepParams& C, int ns, int ny, int nu, int m, void* stream,
-                             int* solver);
+int cmpc_launch_control_step(const ControlStepParams& C, const cmpc_dims& d, void* stream);
 
 // One Jacobi iteration of the sub-controller-sharded cooperative loop
 // (coupled.hip).
@@ -291,18 +291,18 @@ struct CoupledParams {
   uint32_t flags;
 };
 
-// Kernel launchers (cmpc_kernels.hip, produce.hip, coupled.hip).  Return 0 or -1 (unsupported dims).
-int cmpc_launch_build(const BuildParams& P, int ns, int ny, int nu, int m,
-                      void* stream);
-// Row-layout build kernel (build_rows.hip); -1 when not instantiated / not usable.
-int cmpc_launch_build_rows(const BuildParams& P, int ns, int ny, int nu, int m,
-                           void* stream);
+// Kernel launchers.  Which one runs is decided before the call
+// (cmpc_dispatch_plan, dispatch.h); a launcher only launches.  Each checks its
+// availability predicate once more and returns -1 where it is false: the plan
+// and the launcher disagree, an internal error and never a fallback.
+int cmpc_launch_build(const BuildParams& P, const cmpc_dims& d, void* stream);  // P.split: the role-split kernel
+// Row-layout build kernel (build_rows.hip)
+int cmpc_launch_build_rows(const BuildParams& P, const cmpc_dims& d, void* stream);
 // Fused step (step_rows.hip): the row build kernel running the K Jacobi
-// iterations of its QPs itself (P.sv); -1 when not available.  *solver:
-// the solver it runs (CMPC_SOLVE_ROWS or CMPC_SOLVE_LANE).
-int cmpc_launch_step_rows(const BuildParams& P, int ns, int ny, int nu, int m, void* stream, int* solver);
+// iterations of its QPs itself (P.sv) with `solver` (cmpc_step_rows_solver)
+int cmpc_launch_step_rows(const BuildParams& P, const cmpc_dims& d, int solver, void* stream);
 // the same on the one-QP-per-wave build kernel (cmpc_kernels.hip)
-int cmpc_launch_step_wave(const BuildParams& P, int ns, int ny, int nu, int m, void* stream, int* solver);
+int cmpc_launch_step_wave(const BuildParams& P, const cmpc_dims& d, void* stream);
 // Waves per workgroup the row kernel launches with for layout R (4, 2 or 1;
 // 0: does not fit) (build_rows.hip).
 int cmpc_rows_waves_per_group(const RowsLayout& R);
@@ -315,8 +315,7 @@ void cmpc_rows_layout(const cmpc_dims& d, int nd, int nobs, int rec_len, RowsLay
 double cmpc_rows_layout_conflicts(const cmpc_dims& d, int nd, const RowsLayout& R, int wave);
 int cmpc_launch_solve(const SolveParams& P, int nV, int nu, int nVo,
                       void* stream);
-// Row-layout iterate kernel (solve_rows.hip): one QP per 16-lane row;
-// -1 when not instantiated for these dimensions or S does not divide 4.
+// Row-layout iterate kernel (solve_rows.hip): one QP per 16-lane row
 int cmpc_launch_solve_rows(const SolveParams& P, int nV, int nu, int nVo, void* stream);
 int cmpc_launch_qp_batch(const QpBatchParams& P, int n, int nu, void* stream);
 int cmpc_launch_qp_batch_map(const QpBatchParams& P, int n, int nu, int nvo, void* stream);

@@ -27,7 +27,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "cmpc_internal.h"
+#include "dispatch.h"
 #include "dpp_blocks.inc"
 #include "observer_body.h"
 #include "produce_body.h"
@@ -884,38 +884,29 @@ void cmpc_control_step_kernel(ControlStepParams C) {
 // FUSE_: the solve after the build; FUSES_: the same with the role-split
 // build (up to one QP per CU: the coop row solver, faster there)
 #define CONTROL_CASE(NS_, NY_, NU_, M_, FUSE_, FUSES_)                                      \
-  if (ns == NS_ && ny == NY_ && nu == NU_ && m == M_ && P.nd == 2 && P.nu_tot == 4) {        \
+  if (d.ns == NS_ && d.ny == NY_ && d.nu == NU_ && d.m == M_) {                             \
     auto k_ = P.split ? cmpc_control_step_kernel<NS_, NY_, 4, NU_, M_, 2, FUSES_, true>       \
                       : cmpc_control_step_kernel<NS_, NY_, 4, NU_, M_, 2, FUSE_>;            \
-    if (lds > 64 * 1024)                                                                      \
-      cmpc_allow_lds(reinterpret_cast<const void*>(k_), lds);        \
-    const int f_ = P.split ? FUSES_ : FUSE_;                                                  \
-    *solver = (f_ == 1 || f_ == 5) ? CMPC_SOLVE_ROWS : CMPC_SOLVE_LANE;                       \
+    if (lds > 64 * 1024) cmpc_allow_lds(reinterpret_cast<const void*>(k_), lds);            \
     cmpc_launch(k_, dim3(std::max(1, P.grid)), dim3(64 * CMPC_BUILD_WAVES), lds, s, C);      \
     return 0;                                                                                 \
   }
+#define CONTROL_CENT_CASE(NS_, NY_, NU_, M_) CONTROL_CASE(NS_, NY_, NU_, M_, 1, 1)
+#define CONTROL_DIST_CASE(NS_, NY_, NU_, M_) CONTROL_CASE(NS_, NY_, NU_, M_, 3, 5)
 
-int cmpc_launch_control_step(const ControlStepParams& C, int ns, int ny, int nu, int m, void* stream,
-                             int* solver) {
+static_assert(cmpc_prod::kScnLds == kProduceRowLds, "dispatch.h: the producer's LDS per row");
+
+int cmpc_launch_control_step(const ControlStepParams& C, const cmpc_dims& d, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const BuildParams& P = C.b;
   // (P.split: two QP slots per workgroup, the role-split build)
-  if (P.grid * (P.split ? CMPC_BUILD_WAVES / 2 : CMPC_BUILD_WAVES) < P.nqp || P.sv.trace) return -1;
-  if (C.pr.S != P.S || !C.pr.per_qp || !C.pr.obs_M) return -1;
+  if (!cmpc_control_solver(d, P, P.split, P.grid, P.sv.trace != nullptr, C.pr_off) || C.pr.S != P.S ||
+      !C.pr.per_qp || !C.pr.obs_M)
+    return -1;
   size_t lds = sizeof(double) * ((size_t)P.lds_block + (size_t)P.lds_per_wave * CMPC_BUILD_WAVES);
   lds = std::max(lds, sizeof(double) * ((size_t)C.pr_off + 4 * cmpc_prod::kScnLds));
-  if (lds > 160 * 1024) return -1;
-  if (P.S == 1) {
-    if (P.lds_per_wave < ny * (m * 4 + 1) * (nu * m) + 4 * (nu * m) * (nu * m)) return -1;
-    CONTROL_CASE(11, 3, 4, 2, 1, 1)  // parallel centralized
-    CONTROL_CASE(10, 4, 4, 2, 1, 1)  // serial centralized
-    return -1;
-  }
-  if ((P.split ? CMPC_BUILD_WAVES / 2 : CMPC_BUILD_WAVES) % P.S) return -1;
-  CONTROL_CASE(11, 3, 2, 2, 3, 5)  // parallel coop
-  CONTROL_CASE(11, 2, 2, 2, 3, 5)  // parallel ncoop
-  CONTROL_CASE(10, 2, 2, 2, 3, 5)  // serial ncoop
-  CONTROL_CASE(10, 4, 2, 2, 3, 5)  // serial coop
+  CMPC_FOR_CONTROL_CENT(CONTROL_CENT_CASE)
+  CMPC_FOR_CONTROL_DIST(CONTROL_DIST_CASE)
   return -1;
 }
 
@@ -1023,38 +1014,40 @@ __global__ __launch_bounds__(CMPC_SOLVE_THREADS) void cmpc_qp_batch_kernel(QpBat
 // ---------------------------------------------------------------------------
 // launchers — explicit instantiation list (cf. the reference's *_list.h)
 // ---------------------------------------------------------------------------
+#define DIMS_ARE(NS_, NY_, NU_, M_) (d.ns == NS_ && d.ny == NY_ && d.nu == NU_ && d.m == M_)
+
 #define BUILD_CASE(NS_, NY_, NU_, M_)                                                  \
-  if (ns == NS_ && ny == NY_ && nu == NU_ && m == M_ && P.nd == 2 && P.nu_tot == 4) {                   \
-    {                                                                                  \
-      if (P.split) {                                                                   \
-        const size_t lds2 = split_lds_bytes(P, NY_);                                   \
-        auto k2_ = cmpc_build_split_kernel<NS_, NY_, 4, NU_, M_, 2>;                   \
-        if (lds2 > 64 * 1024) cmpc_allow_lds(reinterpret_cast<const void*>(k2_), lds2); \
-        cmpc_launch(k2_, dim3(P.nqp), dim3(128), lds2, s, P);                          \
-        return 0;                                                                      \
-      }                                                                                \
+  if (DIMS_ARE(NS_, NY_, NU_, M_)) {                                                   \
+    if (P.split) {                                                                     \
+      const size_t lds2 = split_lds_bytes(P, NY_);                                     \
+      auto k2_ = cmpc_build_split_kernel<NS_, NY_, 4, NU_, M_, 2>;                     \
+      if (lds2 > 64 * 1024) cmpc_allow_lds(reinterpret_cast<const void*>(k2_), lds2);  \
+      cmpc_launch(k2_, dim3(P.nqp), dim3(128), lds2, s, P);                            \
+      return 0;                                                                        \
     }                                                                                  \
-    const size_t lds = sizeof(double) * ((size_t)P.lds_block +                         \
-                                         (size_t)P.lds_per_wave * CMPC_BUILD_WAVES);  \
-    if (lds > 64 * 1024)                                                               \
-      cmpc_allow_lds(reinterpret_cast<const void*>(cmpc_build_kernel<NS_, NY_, 4, NU_, M_, 2>), lds);                       \
-    int per_cu = cmpc_blocks_per_cu(cmpc_build_kernel<NS_, NY_, 4, NU_, M_, 2>,        \
-                                    64 * CMPC_BUILD_WAVES, lds);                       \
+    auto k_ = cmpc_build_kernel<NS_, NY_, 4, NU_, M_, 2>;                              \
+    if (lds > 64 * 1024) cmpc_allow_lds(reinterpret_cast<const void*>(k_), lds);       \
+    int per_cu = cmpc_blocks_per_cu(k_, 64 * CMPC_BUILD_WAVES, lds);                   \
     if (per_cu < 1) per_cu = std::max<int>(1, (int)((160 * 1024) / lds));             \
     const int grid = std::max(1, std::min(P.grid, P.cus * per_cu));                   \
-    cmpc_launch((cmpc_build_kernel<NS_, NY_, 4, NU_, M_, 2>), dim3(grid),                  \
-                dim3(64 * CMPC_BUILD_WAVES), lds, s, P);                               \
+    cmpc_launch(k_, dim3(grid), dim3(64 * CMPC_BUILD_WAVES), lds, s, P);               \
     return 0;                                                                          \
   }
 
-// fused build + K iterations on the one-QP-per-wave kernel, row solver in
-// the QP's own wave (S = 1)
-#define STEP_WAVE_CASE(NS_, NY_, NU_, M_)                                                \
-  if (ns == NS_ && ny == NY_ && nu == NU_ && m == M_ && P.nd == 2 && P.nu_tot == 4) {   \
-    if (P.lds_per_wave < NY_ * (M_ * 4 + 1) * (NU_ * M_) + 4 * (NU_ * M_) * (NU_ * M_)) \
-      return -1;                                                                         \
-    const size_t lds = sizeof(double) * ((size_t)P.lds_block +                           \
-                                         (size_t)P.lds_per_wave * CMPC_BUILD_WAVES);    \
+// fused build + K iterations on the one-QP-per-wave kernel: FUSE_ / FUSET_
+// (with a trace) 1 / 2 the row solver in the QP's own wave (S = 1), 3 / 4 the
+// lane solver of wave 0 after a workgroup barrier (S divides 4, the
+// scenario's sub-controllers in adjacent waves of one workgroup)
+#define STEP_WAVE_LAUNCH(NS_, NY_, NU_, M_, FUSE_, FUSET_)                               \
+  {                                                                                      \
+    auto k_ = P.sv.trace ? cmpc_build_kernel<NS_, NY_, 4, NU_, M_, 2, FUSET_>            \
+                         : cmpc_build_kernel<NS_, NY_, 4, NU_, M_, 2, FUSE_>;            \
+    if (lds > 64 * 1024) cmpc_allow_lds(reinterpret_cast<const void*>(k_), lds);         \
+    cmpc_launch(k_, dim3(std::max(1, P.grid)), dim3(64 * CMPC_BUILD_WAVES), lds, s, P);   \
+    return 0;                                                                            \
+  }
+#define STEP_WAVE_ROW_CASE(NS_, NY_, NU_, M_)                                            \
+  if (DIMS_ARE(NS_, NY_, NU_, M_)) {                                                     \
     if constexpr (NY_ < 4 && CMPC_STEP_SPLIT_BUILD) {                                    \
       if (P.nqp <= 4 * P.cus) {                                                          \
         const size_t lds2 = split_lds_bytes(P, NY_);                                     \
@@ -1065,78 +1058,39 @@ __global__ __launch_bounds__(CMPC_SOLVE_THREADS) void cmpc_qp_batch_kernel(QpBat
         return 0;                                                                        \
       }                                                                                  \
     }                                                                                    \
-    if (P.sv.trace) {                                                                    \
-      auto k_ = cmpc_build_kernel<NS_, NY_, 4, NU_, M_, 2, 2>;                           \
-      if (lds > 64 * 1024)                                                               \
-        cmpc_allow_lds(reinterpret_cast<const void*>(k_), lds); \
-      cmpc_launch(k_, dim3(std::max(1, P.grid)), dim3(64 * CMPC_BUILD_WAVES), lds, s, P); \
-    } else {                                                                             \
-      auto k_ = cmpc_build_kernel<NS_, NY_, 4, NU_, M_, 2, 1>;                           \
-      if (lds > 64 * 1024)                                                               \
-        cmpc_allow_lds(reinterpret_cast<const void*>(k_), lds); \
-      cmpc_launch(k_, dim3(std::max(1, P.grid)), dim3(64 * CMPC_BUILD_WAVES), lds, s, P); \
-    }                                                                                    \
-    return 0;                                                                            \
+    STEP_WAVE_LAUNCH(NS_, NY_, NU_, M_, 1, 2)                                            \
   }
-
-// the same with the lane solver after a workgroup barrier (S divides 4, the
-// scenario's sub-controllers in adjacent waves of one workgroup)
-#define STEP_WAVE_LANE_CASE(NS_, NY_, NU_, M_)                                           \
-  if (ns == NS_ && ny == NY_ && nu == NU_ && m == M_ && P.nd == 2 && P.nu_tot == 4) {   \
-    const size_t lds = sizeof(double) * ((size_t)P.lds_block +                           \
-                                         (size_t)P.lds_per_wave * CMPC_BUILD_WAVES);    \
-    auto k_ = P.sv.trace ? cmpc_build_kernel<NS_, NY_, 4, NU_, M_, 2, 4>                 \
-                         : cmpc_build_kernel<NS_, NY_, 4, NU_, M_, 2, 3>;                \
-    if (lds > 64 * 1024)                                                                 \
-      cmpc_allow_lds(reinterpret_cast<const void*>(k_), lds);   \
-    *solver = CMPC_SOLVE_LANE;                                                           \
-    cmpc_launch(k_, dim3(std::max(1, P.grid)), dim3(64 * CMPC_BUILD_WAVES), lds, s, P);   \
-    return 0;                                                                            \
-  }
+#define STEP_WAVE_LANE_CASE(NS_, NY_, NU_, M_) \
+  if (DIMS_ARE(NS_, NY_, NU_, M_)) STEP_WAVE_LAUNCH(NS_, NY_, NU_, M_, 3, 4)
 
 // one workgroup per four QPs (no persistent loop: the fused path is for
 // batches that give fewer waves than the GPU holds, each wave one QP)
-int cmpc_launch_step_wave(const BuildParams& P, int ns, int ny, int nu, int m, void* stream, int* solver) {
+int cmpc_launch_step_wave(const BuildParams& P, const cmpc_dims& d, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (P.grid * CMPC_BUILD_WAVES < P.nqp) return -1;
-  if (P.S == 1) {
-    *solver = CMPC_SOLVE_ROWS;
-    STEP_WAVE_CASE(11, 3, 4, 2)  // parallel centralized
-    STEP_WAVE_CASE(10, 4, 4, 2)  // serial centralized
-    return -1;
+  const int solver = cmpc_step_wave_solver(d, P);
+  const size_t lds = sizeof(double) * ((size_t)P.lds_block + (size_t)P.lds_per_wave * CMPC_BUILD_WAVES);
+  if (solver == CMPC_SOLVE_ROWS) {
+    CMPC_FOR_STEP_WAVE_ROW(STEP_WAVE_ROW_CASE)
+  } else if (solver == CMPC_SOLVE_LANE) {
+    CMPC_FOR_STEP_WAVE_LANE(STEP_WAVE_LANE_CASE)
   }
-  if (CMPC_BUILD_WAVES % P.S) return -1;
-  STEP_WAVE_LANE_CASE(11, 3, 2, 2)  // parallel coop
-  STEP_WAVE_LANE_CASE(11, 2, 2, 2)  // parallel ncoop
-  STEP_WAVE_LANE_CASE(10, 2, 2, 2)  // serial ncoop
-  STEP_WAVE_LANE_CASE(10, 4, 2, 2)  // serial coop
   return -1;
 }
 
-int cmpc_launch_build(const BuildParams& P, int ns, int ny, int nu, int m, void* stream) {
+int cmpc_launch_build(const BuildParams& P, const cmpc_dims& d, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  BUILD_CASE(11, 3, 2, 2)  // parallel coop        (ControlledOutputIndices <0,1,3>)
-  BUILD_CASE(11, 2, 2, 2)  // parallel ncoop       (NCControlledOutputIndices)
-  BUILD_CASE(11, 3, 4, 2)  // parallel centralized
-  BUILD_CASE(10, 2, 2, 2)  // serial ncoop
-  BUILD_CASE(10, 4, 2, 2)  // serial coop          (NullIndexArray<4>: all four outputs)
-  BUILD_CASE(10, 4, 4, 2)  // serial centralized
-  BUILD_CASE(11, 3, 2, 1)
-  BUILD_CASE(11, 3, 2, 3)
+  if (!cmpc_build_wave_available(d, P)) return -1;
+  const size_t lds = sizeof(double) * ((size_t)P.lds_block + (size_t)P.lds_per_wave * CMPC_BUILD_WAVES);
+  CMPC_FOR_BUILD_WAVE(BUILD_CASE)
   return -1;
 }
 
 #define SOLVE_CASE(N_, NU_, NVO_)                                                      \
   if (nV == N_ && nu == NU_ && nVo == NVO_) {                                          \
-    if (P.qp_len != N_ * N_ + N_ + N_ * NVO_) return -1;                               \
-    const int grid = (P.nqp + CMPC_SOLVE_THREADS - 1) / CMPC_SOLVE_THREADS;            \
-    if (P.du_other) {                                                                  \
-      if (NVO_ == 0 || P.trace) return -1;                                             \
+    if (P.du_other)                                                                    \
       cmpc_launch((cmpc_solve_kernel<N_, NU_, NVO_, false, (NVO_ > 0)>), dim3(grid),   \
                   dim3(CMPC_SOLVE_THREADS), 0, s, P);                                  \
-      return 0;                                                                        \
-    }                                                                                  \
-    if (P.trace)                                                                       \
+    else if (P.trace)                                                                  \
       cmpc_launch((cmpc_solve_kernel<N_, NU_, NVO_, true>), dim3(grid),                \
                   dim3(CMPC_SOLVE_THREADS), 0, s, P);                                  \
     else                                                                               \
@@ -1147,10 +1101,9 @@ int cmpc_launch_build(const BuildParams& P, int ns, int ny, int nu, int m, void*
 
 int cmpc_launch_solve(const SolveParams& P, int nV, int nu, int nVo, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  SOLVE_CASE(4, 2, 4)   // coop / ncoop, S = 2, m = 2
-  SOLVE_CASE(8, 4, 0)   // centralized, m = 2
-  SOLVE_CASE(2, 2, 2)   // m = 1
-  SOLVE_CASE(6, 2, 6)   // m = 3
+  if (!cmpc_solve_lane_available(nV, nu, nVo, P.qp_len, P.trace != nullptr, P.du_other != nullptr)) return -1;
+  const int grid = (P.nqp + CMPC_SOLVE_THREADS - 1) / CMPC_SOLVE_THREADS;
+  CMPC_FOR_SOLVE(SOLVE_CASE)
   return -1;
 }
 
@@ -1207,29 +1160,34 @@ int cmpc_launch_qp_batch_map(const QpBatchParams& P, int n, int nu, int nvo, voi
     hipLaunchKernelGGL((cmpc_qp_batch_map_kernel<N_, NU_, NVO_>), dim3(grid), dim3(CMPC_SOLVE_THREADS), 0, s, P); \
     return 0;                                                                                       \
   }
-  CMPC_QPMAP_CASE(4, 2, 4)
-  CMPC_QPMAP_CASE(6, 2, 6)
-  CMPC_QPMAP_CASE(2, 2, 2)
+  CMPC_FOR_QP_BATCH_MAP(CMPC_QPMAP_CASE)
 #undef CMPC_QPMAP_CASE
   return -1;
 }
 
 bool cmpc_qp_batch_map_supported(int n, int nu, int nvo) {
-  return (n == 4 && nu == 2 && nvo == 4) || (n == 6 && nu == 2 && nvo == 6) || (n == 2 && nu == 2 && nvo == 2);
+#define CMPC_QPMAP_IS(N_, NU_, NVO_) if (n == N_ && nu == NU_ && nvo == NVO_) return true;
+  CMPC_FOR_QP_BATCH_MAP(CMPC_QPMAP_IS)
+#undef CMPC_QPMAP_IS
+  return false;
 }
 
-bool cmpc_qp_batch_supported(int n, int nu) { return (n == 4 && nu == 2) || (n == 8 && nu == 4); }
+bool cmpc_qp_batch_supported(int n, int nu) {
+#define CMPC_QP_IS(N_, NU_) if (n == N_ && nu == NU_) return true;
+  CMPC_FOR_QP_BATCH(CMPC_QP_IS)
+#undef CMPC_QP_IS
+  return false;
+}
 
 int cmpc_launch_qp_batch(const QpBatchParams& P, int n, int nu, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   const int grid = (P.nqp + CMPC_SOLVE_THREADS - 1) / CMPC_SOLVE_THREADS;
-  if (n == 4 && nu == 2) {
-    hipLaunchKernelGGL((cmpc_qp_batch_kernel<4, 2>), dim3(grid), dim3(CMPC_SOLVE_THREADS), 0, s, P);
-    return 0;
+#define CMPC_QP_CASE(N_, NU_)                                                                        \
+  if (n == N_ && nu == NU_) {                                                                        \
+    hipLaunchKernelGGL((cmpc_qp_batch_kernel<N_, NU_>), dim3(grid), dim3(CMPC_SOLVE_THREADS), 0, s, P); \
+    return 0;                                                                                        \
   }
-  if (n == 8 && nu == 4) {
-    hipLaunchKernelGGL((cmpc_qp_batch_kernel<8, 4>), dim3(grid), dim3(CMPC_SOLVE_THREADS), 0, s, P);
-    return 0;
-  }
+  CMPC_FOR_QP_BATCH(CMPC_QP_CASE)
+#undef CMPC_QP_CASE
   return -1;
 }

@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "cmpc_internal.h"
+#include "dispatch.h"
 #include "solve_rows.h"
 
 namespace {
@@ -54,15 +54,10 @@ __global__ __launch_bounds__(CMPC_SOLVE_THREADS) void cmpc_solve_rows_kernel(Sol
 
 #define SOLVE_ROWS_CASE(N_, NU_, NVO_)                                                  \
   if (nV == N_ && nu == NU_ && nVo == NVO_) {                                           \
-    if (P.qp_len != N_ * N_ + N_ + N_ * NVO_) return -1;                                \
-    const int grid = (P.nqp + kRowsPerBlock - 1) / kRowsPerBlock;                       \
-    if (P.du_other) {                                                                   \
-      if (NVO_ == 0 || P.trace) return -1;                                              \
+    if (P.du_other)                                                                     \
       cmpc_launch((cmpc_solve_rows_kernel<N_, NU_, NVO_, false, (NVO_ > 0)>), dim3(grid), \
                   dim3(CMPC_SOLVE_THREADS), 0, s, P);                                   \
-      return 0;                                                                         \
-    }                                                                                   \
-    if (P.trace)                                                                        \
+    else if (P.trace)                                                                   \
       cmpc_launch((cmpc_solve_rows_kernel<N_, NU_, NVO_, true, false>), dim3(grid),     \
                   dim3(CMPC_SOLVE_THREADS), 0, s, P);                                   \
     else                                                                                \
@@ -71,14 +66,10 @@ __global__ __launch_bounds__(CMPC_SOLVE_THREADS) void cmpc_solve_rows_kernel(Sol
     return 0;                                                                           \
   }
 
-// -1: not instantiated for these dimensions, or S does not divide the
-// four rows of a wave (the plan exchange stays inside a wave)
 int cmpc_launch_solve_rows(const SolveParams& P, int nV, int nu, int nVo, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (P.S < 1 || 4 % P.S) return -1;
-  SOLVE_ROWS_CASE(4, 2, 4)   // coop / ncoop, S = 2, m = 2
-  SOLVE_ROWS_CASE(8, 4, 0)   // centralized, m = 2
-  SOLVE_ROWS_CASE(2, 2, 2)   // m = 1
-  SOLVE_ROWS_CASE(6, 2, 6)   // m = 3
+  if (!cmpc_solve_rows_available(nV, nu, nVo, P.S, P.qp_len, P.trace != nullptr, P.du_other != nullptr)) return -1;
+  const int grid = (P.nqp + kRowsPerBlock - 1) / kRowsPerBlock;
+  CMPC_FOR_SOLVE(SOLVE_ROWS_CASE)
   return -1;
 }

@@ -161,15 +161,25 @@ int cmpc_bind_lin(cmpc_ctx* ctx, const double* lin_device);
 
 /* Hot path. */
 int cmpc_build(cmpc_ctx* ctx);
-/* Build-kernel selection for cmpc_build (same H, f, G within rounding):
- * CMPC_BUILD_ROWS four QPs per wave, one per 16-lane DPP row (m <= 2, LDS
- * fits); CMPC_BUILD_WAVE one QP per wave (every instantiated dimension set);
- * CMPC_BUILD_SPLIT one QP per two waves, the DPP chain in one and the gather
- * in the other (every ny, the ny = 4 simulation pre-pass included);
- * CMPC_BUILD_AUTO (default) rows where its LDS fits and the batch fills the
- * SIMDs, else split up to one QP per SIMD, else wave.  WAVE and SPLIT give
- * the same QP bit for bit; ROWS sums in another order (agreement within
- * rounding, 1e-11 relative). */
+/* Kernel selection.  Which kernel an entry point launches is decided by one
+ * host function, cmpc_dispatch_plan (compressor-mpc_amd/csrc/dispatch.cpp),
+ * from the dimensions, the batch, the device's CU count and the three
+ * variants below; its thresholds and the measurements behind them are
+ * beside it and in DESIGN.md §3.0.  cmpc_plan() further down answers the
+ * same question without a device.  With cus = compute units, nqp = B * S:
+ *
+ * Build (cmpc_build; the same H, f, G within rounding):
+ *   CMPC_BUILD_ROWS   four QPs per wave, one per 16-lane DPP row (m <= 2, an
+ *                     LDS layout exists); an error where it is not available
+ *   CMPC_BUILD_WAVE   one QP per wave (every instantiated dimension set)
+ *   CMPC_BUILD_SPLIT  one QP per two waves, the DPP chain in one and the
+ *                     gather in the other (every ny, the ny = 4 simulation
+ *                     pre-pass included)
+ *   CMPC_BUILD_AUTO   (default) rows where available and ceil(nqp / 4) >=
+ *                     4 cus (a row group per SIMD); else split up to
+ *                     nqp <= 4 cus (one QP per SIMD); else wave
+ * WAVE and SPLIT give the same QP bit for bit; ROWS sums in another order
+ * (agreement within rounding, 1e-11 relative). */
 #define CMPC_BUILD_AUTO 0
 #define CMPC_BUILD_WAVE 1
 #define CMPC_BUILD_ROWS 2
@@ -179,32 +189,75 @@ int cmpc_set_build_variant(cmpc_ctx* ctx, int variant);
  * launched (CMPC_BUILD_WAVE, CMPC_BUILD_ROWS or CMPC_BUILD_SPLIT), 0 before the
  * first build, <0 on a null context. */
 int cmpc_last_build_kernel(cmpc_ctx* ctx);
-/* Solve-kernel selection for cmpc_iterate / cmpc_init_warmstart /
- * cmpc_get_input (the same results bit for bit):
- * CMPC_SOLVE_LANE one QP per lane (large batches); CMPC_SOLVE_ROWS one QP per
- * 16-lane DPP row, its H^-1 and matrix-vector products spread over the row
- * (batches that leave most SIMDs idle; needs S | 4); CMPC_SOLVE_AUTO
- * (default) rows for nV >= 6 below CMPC_SOLVE_ROWS_MAX_QP QPs and for smaller
- * nV up to four QPs per SIMD, where available. */
+/* Solve (cmpc_iterate / cmpc_init_warmstart / cmpc_get_input; the same
+ * results bit for bit):
+ *   CMPC_SOLVE_LANE  one QP per lane
+ *   CMPC_SOLVE_ROWS  one QP per 16-lane DPP row, its H^-1 and matrix-vector
+ *                    products spread over the row (needs S | 4; an error
+ *                    where it is not available)
+ *   CMPC_SOLVE_AUTO  (default) rows, where available, for nV >= 6 below
+ *                    16 384 QPs and for smaller nV up to nqp <= 16 cus
+ *                    (four QPs per SIMD); else lane */
 #define CMPC_SOLVE_AUTO 0
 #define CMPC_SOLVE_LANE 1
 #define CMPC_SOLVE_ROWS 2
 int cmpc_set_solve_variant(cmpc_ctx* ctx, int variant);
 /* The solve kernel the last iterate / init / get-input launched. */
 int cmpc_last_solve_kernel(cmpc_ctx* ctx);
-/* cmpc_step as one launch (the build kernel runs the K Jacobi iterations of
- * the QPs it built, H, f, G handed over in registers; the same results bit
- * for bit as cmpc_build + cmpc_iterate with the row solve kernel):
- * CMPC_STEP_SPLIT two launches; CMPC_STEP_FUSED one (an error where no fused
- * kernel exists for the dimensions); CMPC_STEP_AUTO (default) fused for
- * nV >= 6 from one QP per CU up to CMPC_SOLVE_ROWS_MAX_QP QPs, two launches
- * otherwise (measured faster there: DESIGN.md §3.0). */
+/* Step (cmpc_step).  One launch: the build kernel runs the K Jacobi
+ * iterations of the QPs it built, H, f, G handed over in registers (the same
+ * results bit for bit as cmpc_build + cmpc_iterate on the same build kernel).
+ *   CMPC_STEP_SPLIT  two launches
+ *   CMPC_STEP_FUSED  one launch (K > 0): the one-QP-per-wave kernel below a
+ *                    row group per SIMD, else the row kernel; an error where
+ *                    neither has a fused instance for the dimensions
+ *   CMPC_STEP_AUTO   (default) one launch when the build and solve variants
+ *                    are AUTO too, nV >= 6, p >= 50 and cus < nqp <= 4 cus;
+ *                    two launches otherwise (nV <= 4 at every size) */
 #define CMPC_STEP_AUTO 0
 #define CMPC_STEP_SPLIT 1
 #define CMPC_STEP_FUSED 2
 int cmpc_set_step_variant(cmpc_ctx* ctx, int variant);
 /* 1 if the last cmpc_step ran fused, 0 if split, <0 on a null context. */
 int cmpc_last_step_fused(cmpc_ctx* ctx);
+
+/* What the entry points will launch, answered on the host (no device, no
+ * context): the plan of cmpc_dispatch_plan for a batch of dims->B scenarios
+ * on a device of `cus` compute units under the three variants, for calls
+ * with K iterations and `flags` (CMPC_TRACE; CMPC_PLAN_DU_OTHER: the solve is
+ * a cmpc_get_input with the other controllers' plans given).  A context
+ * takes the same plan with its device's CU count. */
+#define CMPC_PLAN_DU_OTHER 0x100u
+/* plan errors: what a call fails with (cmpc_plan_error_string) */
+#define CMPC_PLAN_OK 0
+#define CMPC_PLAN_NO_ROWS_BUILD 1  /* CMPC_BUILD_ROWS forced, not available */
+#define CMPC_PLAN_NO_BUILD 2       /* no build kernel instance for (ns, ny, nu, m) */
+#define CMPC_PLAN_NO_ROWS_SOLVE 3  /* CMPC_SOLVE_ROWS forced, not available */
+#define CMPC_PLAN_NO_SOLVE 4       /* no solve kernel instance for (nV, nu, nVo) */
+#define CMPC_PLAN_NO_FUSED_STEP 5  /* CMPC_STEP_FUSED forced, not available */
+typedef struct cmpc_plan_t {
+  /* cmpc_build */
+  int32_t build_kernel;        /* CMPC_BUILD_WAVE / ROWS / SPLIT; 0 with build_error */
+  int32_t build_error;
+  /* cmpc_iterate / cmpc_init_warmstart / cmpc_get_input */
+  int32_t solve_kernel;        /* CMPC_SOLVE_LANE / ROWS; 0 with solve_error */
+  int32_t solve_error;         /* (the message follows "<entry point>: ") */
+  /* cmpc_step: one launch, or cmpc_build + cmpc_iterate as above; the two
+   * kernels are what cmpc_last_build_kernel / cmpc_last_solve_kernel report
+   * after it */
+  int32_t step_fused;
+  int32_t step_build_kernel, step_solve_kernel;
+  int32_t step_error;          /* CMPC_PLAN_NO_FUSED_STEP or 0 */
+  /* cmpc_control_step: one launch, or the three calls with cmpc_step as above */
+  int32_t control_fused;
+  int32_t control_build_kernel, control_solve_kernel;
+  int32_t control_grid;        /* workgroups of the one launch (0: three calls) */
+  int32_t control_polled;      /* cmpc_control_step_download polls its completion */
+} cmpc_plan_t;
+int cmpc_plan(const cmpc_dims* dims, int cus, int build_variant, int solve_variant, int step_variant,
+              int K, uint32_t flags, cmpc_plan_t* plan);
+/* the text cmpc_last_error() holds after a call that failed with this plan error */
+const char* cmpc_plan_error_string(int plan_error);
 /* Diagnostic (no GPU needed): the row kernel's LDS layout for *dims as
  * cmpc_build chooses it.  Writes the bank-conflict model's extra LDS cycles
  * per wave-step of the horizon loop (wave 0) for the packed layout (regions
@@ -394,12 +447,15 @@ int cmpc_observer_init_host(cmpc_ctx* ctx, int plant, double p_in, double p_out,
 int cmpc_observe_step_host(cmpc_ctx* ctx, const double* u_full, const double* y);
 /* NerveCenter::GetNextInput (include/nerve_center.h:134-182) on the device:
  * cmpc_observe_step(u_full, y) + cmpc_step(K, 0) + cmpc_observe_apply() with
- * the same results bit for bit, as ONE kernel launch for batches of up to
- * four QPs per CU (AUTO variants, no trace): observer a posteriori +
- * linearisation, the QP build,
- * K Jacobi iterations and the a-priori update in one workgroup per four QP
- * slots.  Elsewhere the three calls.  Plans, statuses and nWSR through
- * cmpc_download; u_old has moved by the own first moves. */
+ * the same results bit for bit.  ONE kernel launch (observer a posteriori +
+ * linearisation, the QP build, K Jacobi iterations and the a-priori update,
+ * one workgroup per four QP slots) when K > 0, the step variant is not
+ * CMPC_STEP_SPLIT, the build and solve variants are AUTO, nqp <= 4 cus and
+ * the dimensions have a control-step instance; up to nqp <= cus its build
+ * runs as role-split pairs, two QP slots per workgroup.  Elsewhere the three
+ * calls (cmpc_dispatch_plan, dispatch.cpp; cmpc_plan's control_* fields).
+ * Plans, statuses and nWSR through cmpc_download; u_old has moved by the own
+ * first moves. */
 int cmpc_control_step(cmpc_ctx* ctx, const double* u_full, const double* y, int K);
 int cmpc_control_step_host(cmpc_ctx* ctx, const double* u_full, const double* y, int K);
 /* cmpc_control_step_host + cmpc_download (host arrays in and out; any output

@@ -124,6 +124,45 @@ def test_gpu_auto_kernel_selection(ctype, B, solve, fused, p):
             assert ctx.last_solve_kernel() == solve
 
 
+@pytest.mark.parametrize("ctype,B,p", [("coop", 1, 20), ("coop", 13, 50), ("cent", 1024, 50),
+                                       ("coop", 2048, 20)])   # 4 096 QPs
+def test_gpu_plan_predicts_what_runs(ctype, B, p):
+    """cmpc.plan with the device's own CU count names the kernels that
+    cmpc_last_* report after build, iterate(1), step(2) and control_step."""
+    import torch
+    from cmpc.synthetic import synthetic_operating_points
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    cfg = cmpc.reference_config("par", ctype, p=p)
+    arr = cmpc.controller_arrays(cfg, reference_setup("par", ctype))
+    dims = cmpc.CmpcDims.from_config(cfg, B)
+    x, u, y = synthetic_operating_points(cfg, B, seed=3, n_distinct=4)
+    tx, tu, ty = (torch.from_numpy(a).to("cuda:0") for a in (x, u, y))
+    nq = B * cfg.S
+    rng = np.random.default_rng(5)
+    with cmpc.Context(cfg, B) as ctx:
+        ctx.configure(arr)
+        ctx.set_state(np.zeros((nq, cfg.nu_tot)), np.zeros((nq, cfg.nV)), np.zeros(nq, np.uint32))
+        for s in range(cfg.S):
+            ctx.set_observer(s, 0.01 * rng.normal(size=(ctx.layout.nobs, y.shape[1])))
+        ctx.observer_init(tx.data_ptr(), tu.data_ptr(), ty.data_ptr())
+        pl = cmpc.plan(dims, cus, K=0)
+        ctx.build()
+        assert ctx.last_build_kernel() == pl.build_kernel and not pl.build_error
+        ctx.init_warmstart()
+        assert ctx.last_solve_kernel() == pl.solve_kernel and not pl.solve_error
+        pl = cmpc.plan(dims, cus, K=1)
+        ctx.iterate(1)
+        assert ctx.last_solve_kernel() == pl.solve_kernel and not pl.solve_error
+        pl = cmpc.plan(dims, cus, K=2)
+        ctx.step(2)
+        assert (ctx.last_build_kernel(), ctx.last_solve_kernel(), ctx.last_step_fused()) == \
+            (pl.step_build_kernel, pl.step_solve_kernel, bool(pl.step_fused))
+        ctx.control_step(tu.data_ptr(), ty.data_ptr(), 2)
+        assert (ctx.last_build_kernel(), ctx.last_solve_kernel(), ctx.last_step_fused()) == \
+            (pl.control_build_kernel, pl.control_solve_kernel, bool(pl.control_fused or pl.step_fused))
+        ctx.synchronize()
+
+
 FUSED_CASES = [  # plant, controller, p, K, B scenarios (pinned to the fused kernels; AUTO fuses config 5)
     ("par", "coop", 20, 9, 4096),     # SURVEY config 2: the row build kernel, lane solver
     ("par", "cent", 20, 1, 8192),     # the row build kernel, row solver per group
