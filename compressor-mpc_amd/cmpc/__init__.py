@@ -28,6 +28,7 @@ from .problem import ControllerArrays, controller_arrays, plant_input_from_plans
 __all__ = ["Context", "ControllerConfig", "SetupFile", "reference_config", "reference_setup",
            "reference_observer_gain", "controller_arrays",
            "plant_input_from_plans", "plant_lin_record", "plant_default", "plant_output",
+           "scenario_reference_offsets", "scenario_limits",
            "layout_of", "plan", "plan_error_string", "rows_lds_model", "qp_solve_batch", "CMPC_APPLY_MOVE", "CMPC_TRACE", "CMPC_QP_OK",
            "CMPC_QP_MAX_NWSR", "CMPC_QP_INFEASIBLE", "CMPC_QP_NOT_PD",
            "CMPC_QP_NONFINITE"]
@@ -140,6 +141,36 @@ def qp_solve_batch_map(H, f, G, d, lb, ub, lbA, ubA, nu, ws_in=None, max_chg=10,
     return x, status, nchg, ws_out, trace, ntrace
 
 
+def scenario_reference_offsets(cfg: ControllerConfig, y_offset) -> np.ndarray:
+    """Plant-level setpoint offsets -> slots.  y_offset: (B, n_outputs), one
+    offset per scenario and plant output; returns (B*S, ny) in slot order
+    q = b*S + s, sub-controller s taking its outputs cfg.out_idx[s]
+    (Context.set_scenario_reference)."""
+    y_offset = np.asarray(y_offset, dtype=np.float64)
+    n_out = int(np.max(cfg.out_idx)) + 1
+    if y_offset.ndim != 2 or y_offset.shape[1] < n_out:
+        raise ValueError(f"y_offset must be (B, n_outputs) with n_outputs >= {n_out}, got {y_offset.shape}")
+    oi = np.asarray(cfg.out_idx, dtype=np.int64)[:, :cfg.ny]      # (S, ny)
+    return np.ascontiguousarray(y_offset[:, oi].reshape(y_offset.shape[0] * cfg.S, cfg.ny))
+
+
+def scenario_limits(cfg: ControllerConfig, lower, upper, rate_lower, rate_upper):
+    """Plant-level input limits -> slots.  Each argument: (B, nu_tot) in plant
+    control order; returns four (B*S, nu) arrays in slot order, sub-controller
+    s taking its own inputs cfg.input_order[s][:nu]
+    (Context.set_scenario_constraints)."""
+    io = np.asarray(cfg.input_order, dtype=np.int64)[:, :cfg.nu]  # (S, nu)
+    out = []
+    B = None
+    for name, a in (("lower", lower), ("upper", upper), ("rate_lower", rate_lower), ("rate_upper", rate_upper)):
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != cfg.nu_tot or (B is not None and a.shape[0] != B):
+            raise ValueError(f"{name} must be (B, nu_tot = {cfg.nu_tot}), got {a.shape}")
+        B = a.shape[0]
+        out.append(np.ascontiguousarray(a[:, io].reshape(B * cfg.S, cfg.nu)))
+    return tuple(out)
+
+
 def _torch_runtime_first():
     """torch bundles its own HIP runtime; when the library's runtime opens the
     device first, torch's later initialisation reports no GPUs.  If the
@@ -235,6 +266,63 @@ class Context:
         vp = lambda p: ctypes.c_void_p(p or None)
         check(self.lib.cmpc_bind_state(self._h, vp(u_old_ptr), vp(du_old_ptr), vp(ws_ptr)),
               "cmpc_bind_state")
+
+    # -- per-scenario setpoints and limits (include/cmpc.h) -----------------
+    def set_scenario_reference(self, dy_ref=None):
+        """Per-slot constant setpoint offsets, (B*S, ny) host array in slot
+        order (scenario_reference_offsets maps plant outputs to slots): slot q
+        tracks y_ref[s] + dy_ref[q] over the whole horizon.  None clears."""
+        if dy_ref is None:
+            check(self.lib.cmpc_set_scenario_reference(self._h, None), "cmpc_set_scenario_reference")
+            return
+        dy = np.ascontiguousarray(dy_ref, np.float64)
+        if dy.size != self.nqp * self.cfg.ny:
+            raise ValueError(f"dy_ref must hold B*S*ny = {self.nqp * self.cfg.ny} values, got {dy.shape}")
+        check(self.lib.cmpc_set_scenario_reference(self._h, dptr(dy)), "cmpc_set_scenario_reference")
+
+    def bind_scenario_reference(self, device_ptr: int = 0):
+        """Bind a device-resident (B*S, ny) f64 offset array (0 clears)."""
+        check(self.lib.cmpc_bind_scenario_reference(self._h, ctypes.c_void_p(device_ptr or None)),
+              "cmpc_bind_scenario_reference")
+
+    def set_scenario_constraints(self, lower=None, upper=None, rate_lower=None, rate_upper=None):
+        """Per-slot input limits, four (B*S, nu) host arrays in slot order
+        (scenario_limits maps plant inputs to slots); all None clears."""
+        arrs = [lower, upper, rate_lower, rate_upper]
+        if all(a is None for a in arrs):
+            check(self.lib.cmpc_set_scenario_constraints(self._h, None, None, None, None),
+                  "cmpc_set_scenario_constraints")
+            return
+        c = []
+        for a in arrs:
+            if a is None:
+                c.append(None)
+                continue
+            a = np.ascontiguousarray(a, np.float64)
+            if a.size != self.nqp * self.cfg.nu:
+                raise ValueError(f"each limit array must hold B*S*nu = {self.nqp * self.cfg.nu} values, got {a.shape}")
+            c.append(a)
+        check(self.lib.cmpc_set_scenario_constraints(self._h, *[None if a is None else dptr(a) for a in c]),
+              "cmpc_set_scenario_constraints")
+
+    def bind_scenario_constraints(self, device_ptr: int = 0):
+        """Bind a device-resident (B*S, 4, nu) f64 array, per slot
+        [lower | upper | rate_lower | rate_upper] (0 clears)."""
+        check(self.lib.cmpc_bind_scenario_constraints(self._h, ctypes.c_void_p(device_ptr or None)),
+              "cmpc_bind_scenario_constraints")
+
+    def get_scenario_reference(self) -> np.ndarray:
+        """(B*S, ny): the offsets in force (set or bound); raises if none."""
+        out = np.zeros((self.nqp, self.cfg.ny))
+        check(self.lib.cmpc_get_scenario_reference(self._h, dptr(out)), "cmpc_get_scenario_reference")
+        return out
+
+    def get_scenario_constraints(self):
+        """Four (B*S, nu) arrays: the per-slot limits in force; raises if none."""
+        out = [np.zeros((self.nqp, self.cfg.nu)) for _ in range(4)]
+        check(self.lib.cmpc_get_scenario_constraints(self._h, *[dptr(a) for a in out]),
+              "cmpc_get_scenario_constraints")
+        return tuple(out)
 
     def produce_lin(self, x_ptr: int, u_full_ptr: int, y_ptr: int, dx_aug_ptr: int = 0,
                     Ts: float = 0.05, p_in: float = 1.0, p_out: float = 1.0):

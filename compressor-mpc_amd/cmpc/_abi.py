@@ -120,6 +120,8 @@ EXPORTS = (
     "cmpc_enable_timing", "cmpc_kernel_time", "cmpc_set_timing_stride", "cmpc_plant_dims", "cmpc_plant_default",
     "cmpc_plant_output", "cmpc_plant_lin_record", "cmpc_qp_solve_batch", "cmpc_qp_solve_batch_map", "cmpc_bind_lin",
     "cmpc_bind_state",
+    "cmpc_set_scenario_reference", "cmpc_bind_scenario_reference", "cmpc_set_scenario_constraints",
+    "cmpc_bind_scenario_constraints", "cmpc_get_scenario_reference", "cmpc_get_scenario_constraints",
     "cmpc_produce_lin", "cmpc_download_lin", "cmpc_coupled_iterate", "cmpc_coupled_validate",
     "cmpc_get_input", "cmpc_get_input_host", "cmpc_update_u", "cmpc_update_u_host",
     "cmpc_set_observer", "cmpc_observer_len", "cmpc_observer_init", "cmpc_observe_step",
@@ -175,6 +177,12 @@ def load_library(path: str = LIB_PATH):
         "cmpc_download_lin": ([c_void, P(dbl)], ctypes.c_int),
         "cmpc_bind_lin": ([c_void, c_void], ctypes.c_int),
         "cmpc_bind_state": ([c_void, c_void, c_void, c_void], ctypes.c_int),
+        "cmpc_set_scenario_reference": ([c_void, P(dbl)], ctypes.c_int),
+        "cmpc_bind_scenario_reference": ([c_void, c_void], ctypes.c_int),
+        "cmpc_set_scenario_constraints": ([c_void, P(dbl), P(dbl), P(dbl), P(dbl)], ctypes.c_int),
+        "cmpc_bind_scenario_constraints": ([c_void, c_void], ctypes.c_int),
+        "cmpc_get_scenario_reference": ([c_void, P(dbl)], ctypes.c_int),
+        "cmpc_get_scenario_constraints": ([c_void, P(dbl), P(dbl), P(dbl), P(dbl)], ctypes.c_int),
         "cmpc_build": ([c_void], ctypes.c_int),
         "cmpc_set_build_variant": ([c_void, ctypes.c_int], ctypes.c_int),
         "cmpc_last_build_kernel": ([c_void], ctypes.c_int),

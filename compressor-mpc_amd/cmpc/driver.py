@@ -32,7 +32,7 @@ import time
 
 import numpy as np
 
-from . import CMPC_TRACE, Context
+from . import CMPC_TRACE, Context, scenario_limits, scenario_reference_offsets
 from .configs import ControllerConfig
 from .sim import REF_CONTROL_INDEX, REF_DELAYS, REF_EPS, REF_TS, PlantSimulator
 
@@ -74,10 +74,15 @@ class ClosedLoop:
     x0, u_offset   (B, ns), (B, n_inputs) host arrays: initial plant state and
                    the input offset u_init_full (NerveCenter::Initialize)
     K              Jacobi iterations per step (n-iterations)
+    y_offset       (B, n_outputs) per-scenario constant setpoint offsets per
+                   plant output, or None (set_setpoints changes them later)
+    limits         (lower, upper, rate_lower, rate_upper), each (B, nu_tot) in
+                   plant control order: per-scenario input limits, or None
+    Both are in force before initialize (the first build and the cold solves).
     """
 
     def __init__(self, cfg: ControllerConfig, arrays, M, x0, u_offset, K: int, device: int = 0,
-                 Ts: float = REF_TS, p_in: float = 1.0, p_out: float = 1.0):
+                 Ts: float = REF_TS, p_in: float = 1.0, p_out: float = 1.0, y_offset=None, limits=None):
         import torch
         self.torch = torch
         torch.cuda.init()
@@ -94,6 +99,10 @@ class ClosedLoop:
                            np.zeros(B * S, np.uint32))
         for s in range(S):
             self.ctx.set_observer(s, M[s])
+        if y_offset is not None:
+            self.set_setpoints(y_offset)
+        if limits is not None:
+            self.ctx.set_scenario_constraints(*scenario_limits(cfg, *limits))
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
         self.x0, self.u_offset = t(x0), t(u_offset)
         self.u_ctrl = torch.zeros(B, cfg.nu_tot, dtype=torch.float64, device=dev)  # NerveCenter::u_old_
@@ -117,6 +126,17 @@ class ClosedLoop:
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
         self.u_offset = t(offs[0])
         self._sched = [(float(segments[i - 1][1]), t(offs[i])) for i in range(1, len(segments))]
+
+    def set_setpoints(self, y_offset):
+        """Per-scenario constant setpoint offsets, (B, n_outputs) per plant
+        output, in force from the next build on; None removes them."""
+        if y_offset is None:
+            self.ctx.set_scenario_reference(None)
+            return
+        y_offset = np.asarray(y_offset, dtype=np.float64)
+        if y_offset.ndim != 2 or y_offset.shape[0] != self.B:
+            raise ValueError(f"y_offset must be (B = {self.B}, n_outputs), got {y_offset.shape}")
+        self.ctx.set_scenario_reference(scenario_reference_offsets(self.cfg, y_offset))
 
     def initialize(self, dx_init=None):
         """SimulationSystem(x0, u_offset) + NerveCenter::Initialize(x0, 0,

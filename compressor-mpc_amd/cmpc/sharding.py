@@ -30,7 +30,10 @@ def qp_slice(start: int, count: int, S: int) -> slice:
 
 
 def shard_arrays(rank: int, world: int, S: int, *arrays):
-    """Per-rank views of scenario-major per-QP arrays (leading dim = B*S)."""
+    """Per-rank views of scenario-major per-QP arrays (leading dim = B*S).
+    The per-slot setpoint offsets (B*S, ny) and limit arrays (B*S, nu) of
+    Context.set_scenario_reference / set_scenario_constraints are such
+    arrays: a rank sets the slices of its own scenarios."""
     n_qp = arrays[0].shape[0]
     if n_qp % S:
         raise ValueError("leading dimension must be a multiple of S")

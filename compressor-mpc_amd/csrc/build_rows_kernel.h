@@ -319,6 +319,19 @@ void cmpc_build_rows_kernel(BuildParams P) {
     double uo[NDW];
 #pragma unroll
     for (int k = 0; k < NDW; ++k) uo[k] = (k < ND) ? P.u_old[(size_t)qq * NUT + dinp[k]] : 0.0;
+    // the slot's setpoint offset (BuildParams::dy_ref), in the same round
+    // trip.  (A 32-bit offset from the scalar base, formed here from qq: as a
+    // loop-carried 64-bit address it costs the bench kernel two registers it
+    // does not have, i.e. scratch.)
+    double dyr[NY];
+#pragma unroll
+    for (int o2 = 0; o2 < NY; ++o2) dyr[o2] = 0.0;
+    if (P.dy_ref) {
+      uint32_t qo = (uint32_t)qq * NY;
+      asm volatile("" : "+v"(qo));
+#pragma unroll
+      for (int o2 = 0; o2 < NY; ++o2) dyr[o2] = P.dy_ref[qo + o2];
+    }
     CMPC_T(0)  // staging issue
     if (CMPC_PX != 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     CMPC_T(1)  // staging wait
@@ -342,6 +355,10 @@ void cmpc_build_rows_kernel(BuildParams P) {
     for (int d = 0; d < KX; ++d) kx[d] = (d < ndist) ? xa[d] : 0.0;
 #pragma unroll
     for (int o2 = 0; o2 < NY; ++o2) ky[o2] = srec[P.off_y + o2];
+    // y_prev - dy_ref: the offset reference, exactly (cmpc.h); without offsets
+    // y_prev - 0, the same bits, and no branch among the staged reads
+#pragma unroll
+    for (int o2 = 0; o2 < NY; ++o2) ky[o2] = ky[o2] - dyr[o2];
     // P-chain multipliers: A column j (state lanes), B column c (Markov lanes)
     double mP[NS];
     if (st) {

@@ -143,6 +143,11 @@ struct cmpc_ctx {
   // unless cmpc_bind_state bound external ones
   double *own_u_old = nullptr, *own_du_old = nullptr;
   uint32_t* own_ws = nullptr;
+  // per-slot setpoint offsets (nqp * ny) and limits (nqp * 4 nu) in force, or
+  // null: the context's own buffers (cmpc_set_scenario_*, allocated on first
+  // use) or bound ones (cmpc_bind_scenario_*)
+  const double *sc_dy = nullptr, *sc_limits = nullptr;
+  double *own_sc_dy = nullptr, *own_sc_limits = nullptr;
   int32_t *status = nullptr, *nwsr = nullptr, *ntrace = nullptr;
   char* out_block = nullptr;  // du | status | nwsr in one allocation: one D2H for cmpc_download
   bool out_host = false;      // out_block is page-locked host memory the kernels write in place
@@ -340,6 +345,7 @@ int solve_params(cmpc_ctx* c, SolveParams* P) {
   P->nu_tot = c->d.nu_tot;
   P->qp_len = c->qp_len;
   P->co = c->co;
+  P->limits = c->sc_limits;
   return 0;
 }
 
@@ -360,6 +366,7 @@ int build_params(cmpc_ctx* c, BuildParams& P) {
   P.cfg = c->cfg;
   P.u_old = c->u_old;
   P.qp = c->qp;
+  P.dy_ref = c->sc_dy;
   return 0;
 }
 
@@ -518,7 +525,7 @@ int cmpc_destroy(cmpc_ctx* c) {
                   c->out_host ? nullptr : c->out_block,
                   c->own_ws ? c->own_ws : c->ws,
                   c->trace, c->ntrace, c->obs, c->d_obsM,
-                  c->stage};
+                  c->stage, c->own_sc_dy, c->own_sc_limits};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -687,6 +694,120 @@ int cmpc_bind_state(cmpc_ctx* c, double* u_old, double* du_old, uint32_t* ws) {
   c->u_old = u_old;
   c->du_old = du_old;
   c->ws = ws;
+  return 0;
+}
+
+// Per-slot setpoint offsets and limits (include/cmpc.h).  The host setters
+// stage into the context's own buffers the way cmpc_set_state does; the bind
+// variants check the pointer the way cmpc_bind_state does.
+static int scenario_upload(cmpc_ctx* c, double** own, const double* host, size_t n) {
+  HIP_TRY(hipSetDevice(c->device));
+  if (!*own) HIP_TRY(hipMalloc(own, sizeof(double) * n));
+  HIP_TRY(hipMemcpyAsync(*own, host, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int cmpc_set_scenario_reference(cmpc_ctx* c, const double* dy_ref) {
+  if (!c) return fail("null context");
+  if (!dy_ref) {
+    c->sc_dy = nullptr;
+    return 0;
+  }
+  const int ny = c->d.ny;
+  const size_t n = (size_t)c->nqp * ny;
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(dy_ref[i]))
+      return fail("cmpc_set_scenario_reference: slot " + std::to_string(i / ny) + ": offsets must be finite");
+  if (scenario_upload(c, &c->own_sc_dy, dy_ref, n)) return -1;
+  c->sc_dy = c->own_sc_dy;
+  return 0;
+}
+
+int cmpc_bind_scenario_reference(cmpc_ctx* c, const double* dy_ref_device) {
+  if (!c) return fail("null context");
+  if (dy_ref_device) {
+    if (!device_ptr_ok(c, dy_ref_device, sizeof(double) * (size_t)c->nqp * c->d.ny)) {
+      (void)hipGetLastError();  // a failed pointer query is not a later launch's error
+      return fail("cmpc_bind_scenario_reference: not a device allocation of nqp * ny doubles on the context's device");
+    }
+    if (reinterpret_cast<uintptr_t>(dy_ref_device) % 8)
+      return fail("cmpc_bind_scenario_reference: misaligned array");
+  }
+  c->sc_dy = dy_ref_device;
+  return 0;
+}
+
+int cmpc_set_scenario_constraints(cmpc_ctx* c, const double* lo, const double* up, const double* rlo,
+                                  const double* rup) {
+  if (!c) return fail("null context");
+  const int nnull = !lo + !up + !rlo + !rup;
+  if (nnull == 4) {
+    c->sc_limits = nullptr;
+    return 0;
+  }
+  if (nnull != 0) return fail("cmpc_set_scenario_constraints: give all four limit arrays or none");
+  const int nu = c->d.nu;
+  const size_t nqp = (size_t)c->nqp;
+  std::vector<double> h(nqp * 4 * nu);  // per slot [lower | upper | rate_lower | rate_upper]
+  for (size_t q = 0; q < nqp; ++q)
+    for (int i = 0; i < nu; ++i) {
+      const double l = lo[q * nu + i], u = up[q * nu + i], rl = rlo[q * nu + i], ru = rup[q * nu + i];
+      if (!std::isfinite(l) || !std::isfinite(u) || !std::isfinite(rl) || !std::isfinite(ru))
+        return fail("cmpc_set_scenario_constraints: slot " + std::to_string(q) + ": limits must be finite");
+      if (!(l <= u) || !(rl <= ru))
+        return fail("cmpc_set_scenario_constraints: slot " + std::to_string(q) +
+                    ": constraints must satisfy lower <= upper");
+      double* b = h.data() + q * 4 * nu;
+      b[i] = l;
+      b[nu + i] = u;
+      b[2 * nu + i] = rl;
+      b[3 * nu + i] = ru;
+    }
+  if (scenario_upload(c, &c->own_sc_limits, h.data(), h.size())) return -1;
+  c->sc_limits = c->own_sc_limits;
+  return 0;
+}
+
+int cmpc_bind_scenario_constraints(cmpc_ctx* c, const double* limits_device) {
+  if (!c) return fail("null context");
+  if (limits_device) {
+    if (!device_ptr_ok(c, limits_device, sizeof(double) * (size_t)c->nqp * 4 * c->d.nu)) {
+      (void)hipGetLastError();  // a failed pointer query is not a later launch's error
+      return fail("cmpc_bind_scenario_constraints: not a device allocation of nqp * 4 nu doubles on the "
+                  "context's device");
+    }
+    if (reinterpret_cast<uintptr_t>(limits_device) % 8)
+      return fail("cmpc_bind_scenario_constraints: misaligned array");
+  }
+  c->sc_limits = limits_device;
+  return 0;
+}
+
+int cmpc_get_scenario_reference(cmpc_ctx* c, double* dy_ref) {
+  if (!c || !dy_ref) return fail("null argument");
+  if (!c->sc_dy) return fail("cmpc_get_scenario_reference: no per-slot offsets are set");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(dy_ref, c->sc_dy, sizeof(double) * (size_t)c->nqp * c->d.ny, hipMemcpyDeviceToHost,
+                         c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int cmpc_get_scenario_constraints(cmpc_ctx* c, double* lo, double* up, double* rlo, double* rup) {
+  if (!c) return fail("null context");
+  if (!c->sc_limits) return fail("cmpc_get_scenario_constraints: no per-slot limits are set");
+  HIP_TRY(hipSetDevice(c->device));
+  const int nu = c->d.nu;
+  const size_t nqp = (size_t)c->nqp;
+  std::vector<double> h(nqp * 4 * nu);
+  HIP_TRY(hipMemcpyAsync(h.data(), c->sc_limits, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  double* out[4] = {lo, up, rlo, rup};
+  for (int k = 0; k < 4; ++k)
+    if (out[k])
+      for (size_t q = 0; q < nqp; ++q)
+        std::memcpy(out[k] + q * nu, h.data() + (q * 4 + k) * nu, sizeof(double) * nu);
   return 0;
 }
 
@@ -1722,6 +1843,7 @@ int cmpc_coupled_iterate(cmpc_ctx* c, int S_total, int S_local, int s_offset, co
   std::memset(&P, 0, sizeof P);
   P.qp = c->qp;
   P.cfg = c->cfg;
+  P.limits = c->sc_limits;
   P.co = c->co;
   P.u_old = c->u_old;
   P.du_old = c->du_old;

@@ -103,7 +103,9 @@ __host__ __device__ constexpr int cmpc_rows_unroll(int ny) { return ny == 2 ? CM
 //   [lwt  : ny*ny ]  L_W' with ywt = L_W L_W' (upper triangular)
 //   [yhat : p*ny  ]  L_W' y_ref_r
 //   [uwt  : nu*nu ]  input weight block of R = blkdiag_m(uwt)
-//   [lower, upper, rate_lower, rate_upper : nu each]
+//   [lower, upper, rate_lower, rate_upper : nu each]  contiguous, in this order:
+//     the solve bodies read them from one base pointer, co.lower or a slot's
+//     own block of SolveParams::limits
 struct CfgOffsets {
   int lwt, yhat, uwt, lower, upper, rlower, rupper, len;
 };
@@ -148,6 +150,8 @@ struct SolveParams {
   int init;           // 1: InitializeQPProblem (cold, f only, ws only)
   const double* du_other;  // nqp * nVo other controllers' plans (cmpc_get_input), or null:
                            // the in-scenario exchange of cmpc_iterate
+  const double* limits;    // nqp * 4 nu per-slot [lower | upper | rate_lower | rate_upper]
+                           // (cmpc_set_scenario_constraints), or null: the cfg block's
 };
 
 struct BuildParams {
@@ -155,6 +159,8 @@ struct BuildParams {
   const double* cfg;     // S * cfg.len
   const double* u_old;   // nqp * nu_tot
   double* qp;            // nqp * qp_len   [H nV*nV | f nV | G nV*nVo]
+  const double* dy_ref;  // nqp * ny per-slot setpoint offsets, applied as y_prev - dy_ref
+                         // (cmpc_set_scenario_reference), or null
   int nqp, S, p, nu_tot, ndist, nd, dmax, rec_len, qp_len;
   int off_A, off_B, off_C, off_f, off_x, off_y, nobs;
   CfgOffsets co;
@@ -278,6 +284,7 @@ int cmpc_launch_control_step(const ControlStepParams& C, const cmpc_dims& d, voi
 struct CoupledParams {
   const double* qp;       // nqp * qp_len (H, f from cmpc_build)
   const double* cfg;
+  const double* limits;   // nqp * 4 nu per-slot limits or null (SolveParams::limits)
   CfgOffsets co;
   double* u_old;          // nqp * nu_tot
   double* du_old;         // nqp * nV

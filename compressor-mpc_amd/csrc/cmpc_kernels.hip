@@ -376,6 +376,15 @@ __device__ __forceinline__ void build_wave_body(const BuildParams& P) {
     const int s = q % S;
     const double* yl = yl_all + s * P.yl_stride;
     const double* lwt = lw_all + s * NY * NY;
+    // the slot's setpoint offset (BuildParams::dy_ref), requested here so that
+    // the staging below covers its latency
+    double dyr[NY];
+#pragma unroll
+    for (int o2 = 0; o2 < NY; ++o2) dyr[o2] = 0.0;
+    if (P.dy_ref) {
+#pragma unroll
+      for (int o2 = 0; o2 < NY; ++o2) dyr[o2] = P.dy_ref[(size_t)q * NY + o2];
+    }
     // record -> LDS, then issue the next record's loads
 #pragma unroll
     for (int i = 0; i < NCH; ++i) {
@@ -427,7 +436,7 @@ __device__ __forceinline__ void build_wave_body(const BuildParams& P) {
       for (int d = 0; d < P.ndist; ++d) t += chat[row * nobs + NS + d] * xa[d];
 #pragma unroll
       for (int o2 = 0; o2 < NY; ++o2)
-        if (o2 >= row) t += lwt[row * NY + o2] * yp[o2];
+        if (o2 >= row) t += lwt[row * NY + o2] * (P.dy_ref ? yp[o2] - dyr[o2] : yp[o2]);
       kap[row] = t;
     }
     if constexpr (PRE) if (wA) {

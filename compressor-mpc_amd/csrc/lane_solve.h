@@ -44,12 +44,15 @@ __device__ __forceinline__ void lane_solve_qp(const SolveParams& P, int q, bool 
   double uo[NU];
 #pragma unroll
   for (int c = 0; c < NU; ++c) uo[c] = P.u_old[(size_t)q * P.nu_tot + c];
+  // the slot's own limits (cmpc_set_scenario_constraints) or the
+  // sub-controller's: [lower | upper | rate_lower | rate_upper] either way
+  const double* lim = P.limits ? P.limits + (size_t)q * (4 * NU) : cfg + P.co.lower;
 #pragma unroll
   for (int c = 0; c < NU; ++c) {
-    qp.lb[c] = cfg[P.co.lower + c] - uo[c];
-    qp.ub[c] = cfg[P.co.upper + c] - uo[c];
-    qp.lbA[c] = cfg[P.co.rlower + c];
-    qp.ubA[c] = cfg[P.co.rupper + c];
+    qp.lb[c] = lim[c] - uo[c];
+    qp.ub[c] = lim[NU + c] - uo[c];
+    qp.lbA[c] = lim[2 * NU + c];
+    qp.ubA[c] = lim[3 * NU + c];
   }
   qp.tolerances();
   const bool pd = hinv_of<N>(H, qp.Hinv);

@@ -39,12 +39,14 @@ __device__ __forceinline__ void rows_solve_qp(const SolveParams& P, int q, bool 
   if constexpr (NVO > 0) {
     if (own) dprev_l = P.du_old[(size_t)q * N + l];
   }
+  // the slot's own limits or the sub-controller's (lane_solve.h)
+  const double* lim = P.limits ? P.limits + (size_t)q * (4 * NU) : cfg + P.co.lower;
 #pragma unroll
   for (int c = 0; c < NU; ++c) {
-    qp.lb[c] = cfg[P.co.lower + c] - uo[c];
-    qp.ub[c] = cfg[P.co.upper + c] - uo[c];
-    qp.lbA[c] = cfg[P.co.rlower + c];
-    qp.ubA[c] = cfg[P.co.rupper + c];
+    qp.lb[c] = lim[c] - uo[c];
+    qp.ub[c] = lim[NU + c] - uo[c];
+    qp.lbA[c] = lim[2 * NU + c];
+    qp.ubA[c] = lim[3 * NU + c];
   }
   qp.tolerances();
   const RowScan sc = row_scan_consts<N, NU>(qp, l);

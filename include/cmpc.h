@@ -159,6 +159,47 @@ int cmpc_download_lin(cmpc_ctx* ctx, double* lin_host);
  * freed and re-allocated at the same address is not re-checked. */
 int cmpc_bind_lin(cmpc_ctx* ctx, const double* lin_device);
 
+/* Per-scenario setpoints and input limits (slot order q = b*S + s).
+ *
+ * Per slot: a constant setpoint offset dy_ref[q] (ny values) and the four
+ * limit vectors (nu values each).  Slot q then tracks y_ref[s][r] + dy_ref[q]
+ * at every horizon row r, inside its own lower/upper/rate limits.  Shared by
+ * the batch as before: the weights (cmpc_set_weights) and the reference's
+ * shape over the horizon (cmpc_set_reference); a reference that differs
+ * between scenarios in more than a constant is not expressible here.
+ *
+ * The offset is applied in the build kernels as y_prev - dy_ref: the reference
+ * enters the free response only as kappa - L_W' y_ref with kappa = C_dist
+ * x_dist + L_W' y_prev, so a build with the offset computes, bit for bit, what
+ * a build without it computes from records whose y_prev is y_prev - dy_ref
+ * (one FP64 subtraction).  H and G do not depend on it.  The limits replace
+ * the sub-controller's cmpc_set_constraints block in every solve
+ * (cmpc_iterate, cmpc_step, cmpc_control_step, cmpc_init_warmstart,
+ * cmpc_get_input, cmpc_coupled_iterate); lb/ub still subtract the slot's
+ * u_old.  cmpc_qp_solve_batch[_map] take their own per-QP bounds and ignore
+ * both.  With nothing set (the default, and the state after a clear) every
+ * call computes exactly what it did without these arrays.
+ *
+ * cmpc_set_scenario_*: host arrays, validated (finite, lower <= upper,
+ * rate_lower <= rate_upper; the message names the first bad slot) and copied
+ * on the ctx stream into buffers the context owns.  All four limit arrays or
+ * all NULL (clear); a NULL dy_ref clears.
+ * cmpc_bind_scenario_*: device arrays read in place by every later call
+ * (checked as cmpc_bind_state checks: device memory of the ctx device inside
+ * an allocation of the required size, 8-byte aligned); NULL clears.  The
+ * bound limits are one array of B*S*4*nu doubles, per slot
+ * [lower | upper | rate_lower | rate_upper], and are not validated.
+ * cmpc_get_scenario_*: host copies of what is in force (set or bound); -1 if
+ * nothing is.  NULL limit outputs are skipped. */
+int cmpc_set_scenario_reference(cmpc_ctx* ctx, const double* dy_ref /* B*S*ny */);
+int cmpc_bind_scenario_reference(cmpc_ctx* ctx, const double* dy_ref_device /* B*S*ny */);
+int cmpc_set_scenario_constraints(cmpc_ctx* ctx, const double* lower, const double* upper,
+                                  const double* rate_lower, const double* rate_upper); /* each B*S*nu */
+int cmpc_bind_scenario_constraints(cmpc_ctx* ctx, const double* limits_device /* B*S*4*nu */);
+int cmpc_get_scenario_reference(cmpc_ctx* ctx, double* dy_ref);
+int cmpc_get_scenario_constraints(cmpc_ctx* ctx, double* lower, double* upper, double* rate_lower,
+                                  double* rate_upper);
+
 /* Hot path. */
 int cmpc_build(cmpc_ctx* ctx);
 /* Kernel selection.  Which kernel an entry point launches is decided by one
