@@ -29,7 +29,7 @@ __all__ = ["Context", "ControllerConfig", "SetupFile", "reference_config", "refe
            "reference_observer_gain", "controller_arrays",
            "plant_input_from_plans", "plant_lin_record", "plant_default", "plant_output",
            "scenario_reference_offsets", "scenario_limits",
-           "layout_of", "plan", "plan_error_string", "rows_lds_model", "qp_solve_batch", "CMPC_APPLY_MOVE", "CMPC_TRACE", "CMPC_QP_OK",
+           "layout_of", "plan", "predict_available", "plan_error_string", "rows_lds_model", "qp_solve_batch", "CMPC_APPLY_MOVE", "CMPC_TRACE", "CMPC_QP_OK",
            "CMPC_QP_MAX_NWSR", "CMPC_QP_INFEASIBLE", "CMPC_QP_NOT_PD",
            "CMPC_QP_NONFINITE"]
 
@@ -50,6 +50,11 @@ def plan(dims: CmpcDims, cus: int, build: int = CMPC_BUILD_AUTO, solve: int = CM
     check(load_library().cmpc_plan(ctypes.byref(dims), int(cus), int(build), int(solve), int(step), int(K),
                                    int(flags), ctypes.byref(out)), "cmpc_plan")
     return out
+
+
+def predict_available(dims: CmpcDims) -> bool:
+    """Whether Context.predict has a kernel instance for dims (host only)."""
+    return bool(load_library().cmpc_predict_available(ctypes.byref(dims)))
 
 
 def plan_error_string(code: int) -> str:
@@ -449,6 +454,29 @@ class Context:
 
     def synchronize(self):
         check(self.lib.cmpc_synchronize(self._h), "cmpc_synchronize")
+
+    # -- prediction (include/cmpc.h, cmpc_predict) --------------------------
+    def predict(self, du_ptr: int = 0, du_other_ptr: int = 0):
+        """Predicted outputs and objective values of every QP slot for the
+        plans at du_ptr (device, (B*S, nV); 0: the context's current plans)
+        and the other controllers' plans at du_other_ptr (device, (B*S, nVo)
+        in the Jacobi iteration's order; 0: gathered from the scenario's other
+        slots).  Refused unless a build has run and nothing it read has
+        changed since.  Asynchronous; results through download_prediction."""
+        vp = lambda p: ctypes.c_void_p(p or None)
+        check(self.lib.cmpc_predict(self._h, vp(du_ptr), vp(du_other_ptr), 0), "cmpc_predict")
+
+    def download_prediction(self):
+        """(y_pred (B*S, p, ny), cost (B*S, 2) = [J_track, J_move]) of the last predict."""
+        y = np.zeros((self.nqp, self.cfg.p, self.cfg.ny))
+        cost = np.zeros((self.nqp, 2))
+        check(self.lib.cmpc_download_prediction(self._h, dptr(y), dptr(cost)), "cmpc_download_prediction")
+        return y, cost
+
+    def prediction_ptrs(self):
+        """Device addresses of (y_pred, cost); (0, 0) before the first predict."""
+        return (self.lib.cmpc_prediction_device(self._h) or 0,
+                self.lib.cmpc_prediction_cost_device(self._h) or 0)
 
     # -- results ---------------------------------------------------------
     def download(self):

@@ -133,6 +133,8 @@ EXPORTS = (
     "cmpc_sim_synchronize", "cmpc_sim_state", "cmpc_sim_input", "cmpc_sim_step_size",
     "cmpc_sim_status", "cmpc_accumulate_moves", "cmpc_sim_download", "cmpc_sim_reset_host",
     "cmpc_sim_set_input_host", "cmpc_sim_set_offset_host", "cmpc_sim_output_host",
+    "cmpc_predict", "cmpc_predict_host", "cmpc_prediction_device", "cmpc_prediction_cost_device",
+    "cmpc_download_prediction", "cmpc_predict_available",
 )
 
 _lib = None
@@ -258,6 +260,12 @@ def load_library(path: str = LIB_PATH):
                                    ctypes.c_size_t], ctypes.c_int),
         "cmpc_coupled_iterate": ([c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void, ctypes.c_size_t,
                                   c_void, ctypes.c_size_t, c_void, u32], ctypes.c_int),
+        "cmpc_predict": ([c_void, c_void, c_void, u32], ctypes.c_int),
+        "cmpc_predict_host": ([c_void, P(dbl), P(dbl), u32], ctypes.c_int),
+        "cmpc_prediction_device": ([c_void], c_void),
+        "cmpc_prediction_cost_device": ([c_void], c_void),
+        "cmpc_download_prediction": ([c_void, P(dbl), P(dbl)], ctypes.c_int),
+        "cmpc_predict_available": ([P(CmpcDims)], ctypes.c_int),
         "cmpc_qp_solve_batch": ([ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(dbl),
                                  P(dbl), P(dbl), P(dbl), P(dbl), P(dbl), P(u32), ctypes.c_int,
                                  P(dbl), P(i32), P(i32), P(u32), P(ctypes.c_uint8), P(i32)],

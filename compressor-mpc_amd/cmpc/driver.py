@@ -153,11 +153,15 @@ class ClosedLoop:
         self.k = 0
         self.t_seg, self.seg_step = 0.0, 0   # integrate_const's start time and step count
 
-    def step(self, trace: bool = False):
+    def step(self, trace: bool = False, predict: bool = False):
         """One sampling instant: returns (t, y) of the instant; the plant has
         advanced to the next one.  trace: the Jacobi iterations record their
         working-set changes (CMPC_TRACE); self.last_changes is then their
-        total over the K iterations and all QP slots of this instant."""
+        total over the K iterations and all QP slots of this instant.
+        predict: the instant's plans are evaluated against the model they were
+        computed from (Context.predict, before the move is applied);
+        self.last_prediction (B*S, p, ny) and self.last_cost (B*S, 2) are then
+        host arrays.  The step itself computes the same with or without."""
         from ._abi import check, iptr
         t = 0.0 + self.k * self.Ts   # the record's label (record count)
         # integrate_const's own time: start_time + step * dt of the current
@@ -174,6 +178,9 @@ class ClosedLoop:
         if trace:
             _, ntr = self.ctx.download_trace(self.K)
             self.last_changes = int(ntr.sum())
+        if predict:
+            self.ctx.predict()
+            self.last_prediction, self.last_cost = self.ctx.download_prediction()
         self.ctx.observe_apply()
         check(self.ctx.lib.cmpc_accumulate_moves(self.ctx._h, iptr(self.io),
                                                  self.torch_ptr(self.u_ctrl)), "cmpc_accumulate_moves")

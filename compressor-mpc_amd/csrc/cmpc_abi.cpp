@@ -189,6 +189,13 @@ struct cmpc_ctx {
   cmpc_plan_t plans[8];
   unsigned plans_valid = 0;             // bit k: plans[k] holds; cleared by cmpc_set_*_variant
   int last_step_fused = 0;
+  // prediction (cmpc_predict): buffers allocated by the first call; pred_stale
+  // is why a prediction would not describe the last build's QPs (null: a
+  // build has run and nothing it read has changed through the ABI since)
+  double *pred_y = nullptr, *pred_cost = nullptr;
+  bool pred_done = false;
+  bool pred_built = false;  // a build has run
+  const char* pred_stale = nullptr;
   // timing
   int timing = 0;  // bit k: kernel k (CMPC_KERNEL_*) is timed
   int timing_stride = 1;                        // time every stride-th launch
@@ -385,6 +392,9 @@ const cmpc_plan_t& plan_of(cmpc_ctx* c, int K, bool trace, bool du_other) {
   return c->plans[k];
 }
 
+// cmpc_ctx::pred_stale after a solve that applied its first move
+const char* const kStaleMove = "u_old has moved since the build (CMPC_APPLY_MOVE applied the first move)";
+
 int plan_mismatch(const char* what) {
   return fail(std::string("internal error: plan and launcher disagree (") + what + ")");
 }
@@ -525,7 +535,7 @@ int cmpc_destroy(cmpc_ctx* c) {
                   c->out_host ? nullptr : c->out_block,
                   c->own_ws ? c->own_ws : c->ws,
                   c->trace, c->ntrace, c->obs, c->d_obsM,
-                  c->stage, c->own_sc_dy, c->own_sc_limits};
+                  c->stage, c->own_sc_dy, c->own_sc_limits, c->pred_y, c->pred_cost};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -557,6 +567,7 @@ int cmpc_set_weights(cmpc_ctx* c, int s, const double* uwt, const double* ywt) {
   std::memcpy(c->uwt.data() + (size_t)s * nu * nu, uwt, sizeof(double) * nu * nu);
   c->have_w[s] = 1;
   c->cfg_dirty = true;
+  c->pred_stale = "the weights have changed since the build (cmpc_set_weights)";
   return 0;
 }
 
@@ -584,6 +595,7 @@ int cmpc_set_reference(cmpc_ctx* c, int s, const double* y_ref) {
   std::memcpy(c->yref.data() + s * n, y_ref, sizeof(double) * n);
   c->have_r[s] = 1;
   c->cfg_dirty = true;
+  c->pred_stale = "the reference has changed since the build (cmpc_set_reference)";
   return 0;
 }
 
@@ -591,9 +603,11 @@ int cmpc_set_state(cmpc_ctx* c, const double* u_old, const double* du_old, const
   if (!c) return fail("null context");
   HIP_TRY(hipSetDevice(c->device));
   const size_t n = (size_t)c->nqp;
-  if (u_old)
+  if (u_old) {
+    c->pred_stale = "u_old has changed since the build (cmpc_set_state)";
     HIP_TRY(hipMemcpyAsync(c->u_old, u_old, sizeof(double) * n * c->d.nu_tot,
                            hipMemcpyHostToDevice, c->stream));
+  }
   if (du_old)
     HIP_TRY(hipMemcpyAsync(c->du_old, du_old, sizeof(double) * n * c->L.nV,
                            hipMemcpyHostToDevice, c->stream));
@@ -620,6 +634,7 @@ int cmpc_get_state(cmpc_ctx* c, double* u_old, double* du_old, uint32_t* ws) {
 int cmpc_upload_lin(cmpc_ctx* c, const double* lin) {
   if (!c || !lin) return fail("null argument");
   HIP_TRY(hipSetDevice(c->device));
+  c->pred_stale = "the records have changed since the build (cmpc_upload_lin)";
   HIP_TRY(hipMemcpyAsync(c->lin, lin, sizeof(double) * (size_t)c->nqp * c->L.rec_len,
                          hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -671,6 +686,7 @@ int cmpc_bind_lin(cmpc_ctx* c, const double* lin_device) {
       return fail("cmpc_bind_lin: records must be 16-byte aligned");
   }
   c->lin_bound = lin_device;
+  c->pred_stale = "the records have been re-bound since the build (cmpc_bind_lin)";
   return 0;
 }
 
@@ -678,6 +694,7 @@ int cmpc_bind_state(cmpc_ctx* c, double* u_old, double* du_old, uint32_t* ws) {
   if (!c) return fail("null context");
   const int nnull = !u_old + !du_old + !ws;
   if (nnull == 3) {
+    c->pred_stale = "the state has been re-bound since the build (cmpc_bind_state)";
     c->u_old = c->own_u_old;
     c->du_old = c->own_du_old;
     c->ws = c->own_ws;
@@ -694,6 +711,7 @@ int cmpc_bind_state(cmpc_ctx* c, double* u_old, double* du_old, uint32_t* ws) {
   c->u_old = u_old;
   c->du_old = du_old;
   c->ws = ws;
+  c->pred_stale = "the state has been re-bound since the build (cmpc_bind_state)";
   return 0;
 }
 
@@ -711,6 +729,7 @@ static int scenario_upload(cmpc_ctx* c, double** own, const double* host, size_t
 int cmpc_set_scenario_reference(cmpc_ctx* c, const double* dy_ref) {
   if (!c) return fail("null context");
   if (!dy_ref) {
+    if (c->sc_dy) c->pred_stale = "the setpoint offsets have changed since the build (cmpc_set_scenario_reference)";
     c->sc_dy = nullptr;
     return 0;
   }
@@ -719,6 +738,7 @@ int cmpc_set_scenario_reference(cmpc_ctx* c, const double* dy_ref) {
   for (size_t i = 0; i < n; ++i)
     if (!std::isfinite(dy_ref[i]))
       return fail("cmpc_set_scenario_reference: slot " + std::to_string(i / ny) + ": offsets must be finite");
+  c->pred_stale = "the setpoint offsets have changed since the build (cmpc_set_scenario_reference)";
   if (scenario_upload(c, &c->own_sc_dy, dy_ref, n)) return -1;
   c->sc_dy = c->own_sc_dy;
   return 0;
@@ -735,6 +755,7 @@ int cmpc_bind_scenario_reference(cmpc_ctx* c, const double* dy_ref_device) {
       return fail("cmpc_bind_scenario_reference: misaligned array");
   }
   c->sc_dy = dy_ref_device;
+  c->pred_stale = "the setpoint offsets have been re-bound since the build (cmpc_bind_scenario_reference)";
   return 0;
 }
 
@@ -870,6 +891,7 @@ int cmpc_produce_lin(cmpc_ctx* c, int plant, double p_in, double p_out, double T
   P.y = y;
   HIP_TRY(hipSetDevice(c->device));
   c->lin_bound = nullptr;  // the build reads the produced records
+  c->pred_stale = "the records have changed since the build (cmpc_produce_lin)";
   TimedLaunch tl(c, CMPC_KERNEL_PRODUCE);
   if (tl.begin()) return -1;
   if (cmpc_launch_produce(P, plant, c->stream)) return fail("cmpc_produce_lin: launch failed");
@@ -1004,6 +1026,7 @@ static int observer_produce(cmpc_ctx* c, const double* u_full, const double* y, 
   ProduceParams P;
   if (observer_produce_params(c, u_full, y, with_post, P)) return -1;
   c->lin_bound = nullptr;
+  c->pred_stale = "the records have changed since the build (cmpc_observe_step / cmpc_observer_init)";
   TimedLaunch tl(c, CMPC_KERNEL_PRODUCE);
   if (tl.begin()) return -1;
   if (cmpc_launch_produce(P, c->obs_plant, c->stream)) return fail("observer: produce launch failed");
@@ -1062,6 +1085,7 @@ int cmpc_observe_apply(cmpc_ctx* c) {
   HIP_TRY(hipSetDevice(c->device));
   ObserverParams P;
   observer_params(c, &P);
+  c->pred_stale = "u_old has moved since the build (cmpc_observe_apply applied the first move)";
   TimedLaunch tl(c, CMPC_KERNEL_OBSERVE_PRIOR);
   if (tl.begin()) return -1;
   if (cmpc_launch_observer(P, CMPC_OBS_PRIOR, c->stream))
@@ -1101,6 +1125,7 @@ static int control_step(cmpc_ctx* c, const double* u_full, const double* y, int 
   std::memset(&C, 0, sizeof C);
   if (observer_produce_params(c, u_full, y, true, C.pr)) return -1;
   c->lin_bound = nullptr;  // the build reads the produced records
+  c->pred_stale = "the records and u_old have changed since the build (cmpc_control_step applied the first move)";
   if (build_params(c, C.b)) return -1;
   C.b.split = pl.control_build_kernel == CMPC_BUILD_SPLIT;
   C.b.grid = pl.control_grid;
@@ -1119,6 +1144,7 @@ static int control_step(cmpc_ctx* c, const double* u_full, const double* y, int 
   c->last_build = pl.control_build_kernel;
   c->last_solve = pl.control_solve_kernel;
   c->last_step_fused = 1;
+  c->pred_built = true;  // (and stale at once: the a-priori phase has moved u_old)
   c->obs_steps++;  // the delay-block rings advance by one (cmpc_observe_apply)
   if (flagged) *flagged = flag;
   return tl.end();
@@ -1649,6 +1675,8 @@ int cmpc_build(cmpc_ctx* c) {
     return plan_mismatch("build");
   if (check_launch("build kernel")) return -1;
   c->last_build = pl.build_kernel;
+  c->pred_built = true;
+  c->pred_stale = nullptr;
   return tl.end();
 }
 
@@ -1734,6 +1762,7 @@ int cmpc_iterate(cmpc_ctx* c, int K, uint32_t flags) {
   if (solve_kernel_of(c, P, "cmpc_iterate", &kernel)) return -1;
   TimedLaunch tl(c, CMPC_KERNEL_ITERATE);
   if (tl.begin()) return -1;
+  if (flags & CMPC_APPLY_MOVE) c->pred_stale = kStaleMove;
   if (launch_solve(c, P, kernel)) return -1;
   if (check_launch("iterate kernel")) return -1;
   return tl.end();
@@ -1757,6 +1786,7 @@ int cmpc_get_input(cmpc_ctx* c, const double* du_last, uint32_t flags) {
   if (solve_kernel_of(c, P, "cmpc_get_input", &kernel)) return -1;
   TimedLaunch tl(c, CMPC_KERNEL_ITERATE);
   if (tl.begin()) return -1;
+  if (flags & CMPC_APPLY_MOVE) c->pred_stale = kStaleMove;
   if (launch_solve(c, P, kernel)) return -1;
   if (check_launch("get-input kernel")) return -1;
   return tl.end();
@@ -1784,6 +1814,7 @@ int cmpc_update_u(cmpc_ctx* c, const double* du_full) {
   ObserverParams P;
   observer_params(c, &P);
   P.du_full = du_full;
+  c->pred_stale = "u_old has moved since the build (cmpc_update_u)";
   TimedLaunch tl(c, CMPC_KERNEL_OBSERVE_PRIOR);
   if (tl.begin()) return -1;
   if (cmpc_launch_observer(P, CMPC_OBS_PRIOR, c->stream))
@@ -1863,6 +1894,7 @@ int cmpc_coupled_iterate(cmpc_ctx* c, int S_total, int S_local, int s_offset, co
   P.s_offset = s_offset;
   P.B = c->nqp / S_local;
   P.flags = flags;
+  if (flags & CMPC_APPLY_MOVE) c->pred_stale = kStaleMove;
   TimedLaunch tl(c, CMPC_KERNEL_ITERATE);
   if (tl.begin()) return -1;
   if (cmpc_launch_coupled(P, c->L.nV, c->d.nu, c->stream))
@@ -1921,6 +1953,8 @@ int cmpc_step(cmpc_ctx* c, int K, uint32_t flags) {
   c->last_build = pl.step_build_kernel;
   c->last_solve = pl.step_solve_kernel;
   c->last_step_fused = 1;
+  c->pred_built = true;
+  c->pred_stale = (flags & CMPC_APPLY_MOVE) ? kStaleMove : nullptr;
   return tl.end();
 }
 
@@ -1986,6 +2020,84 @@ int cmpc_download_trace(cmpc_ctx* c, uint8_t* trace, int32_t* ntrace) {
   const size_t n = (size_t)c->nqp * c->trace_K;
   if (trace) HIP_TRY(hipMemcpyAsync(trace, c->trace, n * 16, hipMemcpyDeviceToHost, c->stream));
   if (ntrace) HIP_TRY(hipMemcpyAsync(ntrace, c->ntrace, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// Predicted outputs and objective values of every QP slot (predict.hip).
+int cmpc_predict(cmpc_ctx* c, const double* du, const double* du_other, uint32_t flags) {
+  if (!c) return fail("null context");
+  if (flags) return fail("cmpc_predict: flags must be 0 (reserved)");
+  if (!cmpc_predict_instance(c->d, c->L))
+    return fail("cmpc_predict: predict kernel not instantiated for these dimensions (ns, ny, nu, m)");
+  if (!c->pred_built) return fail("cmpc_predict: no build has run (cmpc_build, cmpc_step or cmpc_control_step)");
+  if (c->pred_stale) return fail(std::string("cmpc_predict: ") + c->pred_stale);
+  if (c->L.nVo == 0) du_other = nullptr;
+  if (c->L.nVo > 0 && !du_other && c->L.nuo != (c->d.S - 1) * c->d.nu)
+    return fail("cmpc_predict: the other controllers' plans are not in this context (S = 1, nu < nu_tot): "
+                "give du_other");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = (size_t)c->nqp;
+  if (!c->pred_y) HIP_TRY(hipMalloc(&c->pred_y, sizeof(double) * n * c->d.p * c->d.ny));
+  if (!c->pred_cost) HIP_TRY(hipMalloc(&c->pred_cost, sizeof(double) * n * 2));
+  PredictParams P;
+  std::memset(&P, 0, sizeof P);
+  P.lin = c->lin_bound ? c->lin_bound : c->lin;
+  P.cfg = c->cfg;
+  P.u_old = c->u_old;
+  P.dy_ref = c->sc_dy;
+  P.du = du ? du : c->du;  // (page-locked host memory up to CMPC_HOST_OUT_MAX_QP slots: its device address)
+  P.d = du_other;
+  P.y_pred = c->pred_y;
+  P.cost = c->pred_cost;
+  P.nqp = c->nqp;
+  P.S = c->d.S;
+  P.p = c->d.p;
+  P.ndist = c->d.ndist;
+  P.rec_len = c->L.rec_len;
+  P.nobs = c->L.nobs;
+  P.off_A = c->L.off_A; P.off_B = c->L.off_B; P.off_C = c->L.off_C;
+  P.off_f = c->L.off_f; P.off_x = c->L.off_x; P.off_y = c->L.off_y;
+  P.co = c->co;
+  int kd = 0, blk = c->d.ndist + c->L.nd;
+  for (int i = 0; i < c->d.nu_tot; ++i) {
+    P.delay[i] = c->d.delay[i];
+    if (c->d.delay[i] > 0) {
+      P.dslot[i] = c->d.ndist + kd++;
+      P.dblk[i] = blk;
+      blk += c->d.delay[i] - 1;
+    }
+  }
+  if (cmpc_launch_predict(P, c->d, c->stream)) return plan_mismatch("predict");
+  if (check_launch("predict kernel")) return -1;
+  c->pred_done = true;
+  return 0;
+}
+
+int cmpc_predict_host(cmpc_ctx* c, const double* du, const double* du_other, uint32_t flags) {
+  if (!c) return fail("null context");
+  if (!du && !(du_other && c->L.nVo)) return cmpc_predict(c, nullptr, nullptr, flags);
+  HIP_TRY(hipSetDevice(c->device));
+  const double* h[2] = {du, c->L.nVo ? du_other : nullptr};
+  const size_t n[2] = {(size_t)c->nqp * c->L.nV, (size_t)c->nqp * c->L.nVo};
+  const double* d[2];
+  if (stage_host(c, h, n, 2, d)) return -1;
+  const int rc = cmpc_predict(c, d[0], d[1], flags);
+  return stage_done(c) ? -1 : rc;
+}
+
+double* cmpc_prediction_device(cmpc_ctx* c) { return c && c->pred_done ? c->pred_y : nullptr; }
+double* cmpc_prediction_cost_device(cmpc_ctx* c) { return c && c->pred_done ? c->pred_cost : nullptr; }
+
+int cmpc_download_prediction(cmpc_ctx* c, double* y_pred, double* cost) {
+  if (!c) return fail("null context");
+  if (!c->pred_done) return fail("cmpc_download_prediction: nothing has been predicted (cmpc_predict)");
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = (size_t)c->nqp;
+  if (y_pred)
+    HIP_TRY(hipMemcpyAsync(y_pred, c->pred_y, sizeof(double) * n * c->d.p * c->d.ny, hipMemcpyDeviceToHost,
+                           c->stream));
+  if (cost) HIP_TRY(hipMemcpyAsync(cost, c->pred_cost, sizeof(double) * n * 2, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -193,6 +193,29 @@ struct BuildParams {
 };
 
 
+// Prediction (predict.hip, cmpc_predict): the predicted controlled outputs of
+// every QP slot over the horizon for given plans, and the two parts of the
+// objective.  Reads what the build read (records, u_old, cfg, dy_ref).
+struct PredictParams {
+  const double* lin;     // nqp * rec_len
+  const double* cfg;     // S * co.len
+  const double* u_old;   // nqp * nu_tot
+  const double* dy_ref;  // nqp * ny per-slot setpoint offsets, or null
+  const double* du;      // nqp * nV own plans
+  const double* d;       // nqp * nVo other controllers' plans (the Jacobi iteration's order), or
+                         // null: gathered from du of the scenario's other slots
+  double* y_pred;        // nqp * p * ny
+  double* cost;          // nqp * 2: [J_track, J_move]
+  int nqp, S, p, ndist, rec_len, nobs;
+  int off_A, off_B, off_C, off_f, off_x, off_y;
+  CfgOffsets co;
+  int delay[CMPC_MAX_INPUTS];  // per input
+  int dslot[CMPC_MAX_INPUTS];  // per delayed input: dx_aug index of its delayed-input state
+  int dblk[CMPC_MAX_INPUTS];   // per delayed input: dx_aug index of its shift block's first entry
+};
+// one QP per 16-lane row, four per one-wave workgroup; -1: no instance
+int cmpc_launch_predict(const PredictParams& P, const cmpc_dims& d, void* stream);
+
 // Standalone batched solver (parity / KKT tests).  G (nqp * n * nvo) and d
 // (nqp * nvo) non-null: the Jacobi iteration's map-form solve with g = f + G d
 // (cmpc_qp_solve_batch_map); g is f then.

@@ -285,6 +285,21 @@ bool cmpc_solve_rows_available(int nV, int nu, int nVo, int S, int qp_len, bool 
   return S >= 1 && 4 % S == 0 && cmpc_solve_lane_available(nV, nu, nVo, qp_len, trace, du_other);
 }
 
+bool cmpc_predict_instance(const cmpc_dims& d, const cmpc_layout& L) {
+  if (L.nd != CMPC_DIMS_ND || d.nu_tot != CMPC_DIMS_NUT) return false;
+#define CMPC_PREDICT_IS(NS_, NY_, NU_, M_) \
+  if (d.ns == NS_ && d.ny == NY_ && d.nu == NU_ && d.m == M_) return true;
+  CMPC_FOR_BUILD_WAVE(CMPC_PREDICT_IS)
+#undef CMPC_PREDICT_IS
+  return false;
+}
+
+extern "C" int cmpc_predict_available(const cmpc_dims* dims) {
+  cmpc_layout L;
+  if (cmpc_layout_error(dims, &L) || cmpc_context_dims_error(*dims, L)) return 0;
+  return cmpc_predict_instance(*dims, L) ? 1 : 0;
+}
+
 // ---------------------------------------------------------------------------
 // the policy
 // ---------------------------------------------------------------------------

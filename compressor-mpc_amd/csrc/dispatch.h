@@ -47,6 +47,10 @@ int cmpc_step_rows_solver(const cmpc_dims& d, const BuildParams& P);
 int cmpc_control_solver(const cmpc_dims& d, const BuildParams& P, bool split, int grid, bool trace, int pr_off);
 bool cmpc_solve_lane_available(int nV, int nu, int nVo, int qp_len, bool trace, bool du_other);
 bool cmpc_solve_rows_available(int nV, int nu, int nVo, int S, int qp_len, bool trace, bool du_other);
+// the predict kernel (predict.hip) has an instance: every dimension set with a
+// one-QP-per-wave build instance (cmpc_predict_available, cmpc.h, adds the
+// context's dimension checks)
+bool cmpc_predict_instance(const cmpc_dims& d, const cmpc_layout& L);
 
 // --- the policy ------------------------------------------------------------
 // P: cmpc_dispatch_params of the batch (nqp, cus and the layouts).  K, trace

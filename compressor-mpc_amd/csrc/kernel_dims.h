@@ -18,7 +18,8 @@
 
 // Build side: (ns, ny, nu, m) and, per kernel family, whether the family has
 // an instance for the set.
-//   WAVE  one-QP-per-wave build (cmpc_build_kernel), its role-split form too
+//   WAVE  one-QP-per-wave build (cmpc_build_kernel), its role-split form too;
+//         the predict kernel (predict.hip) is instantiated over this column
 //   ROWS  row build (cmpc_build_rows_kernel)
 //   SWR   fused step on the wave kernel, row solver in the QP's wave (S = 1)
 //   SWL   fused step on the wave kernel, lane solver of wave 0

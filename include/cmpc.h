@@ -322,6 +322,55 @@ int cmpc_download_qp(cmpc_ctx* ctx, double* H, double* f, double* G);
  * 0xFF terminates), ntrace: B*S*K counts. */
 int cmpc_download_trace(cmpc_ctx* ctx, uint8_t* trace, int32_t* ntrace);
 
+/* Prediction: what the controller expects plans to do (the reference hands
+ * out Prediction{Su, Sx, Sf, Su_other}, include/prediction.h,
+ * AugmentedLinearizedSystem::GeneratePrediction, and leaves the products to
+ * the caller).  For QP slot q = b*S + s, its record and u_old as the last
+ * build read them, a plan du (nV) and the other controllers' plans d (nVo, in
+ * the Jacobi iteration's order d[mv*nuo + rank*nu + c], rank = index among the
+ * scenario's other sub-controllers):
+ *   y_pred[r] = y_prev + (Su du + Su_other d + Sf fd + Sx xa)[r],  r = 0..p-1
+ *   e[r]      = y_pred[r] - (y_ref[s][r] + dy_ref[q])
+ *   J_track   = 1/2 sum_r e[r]' ywt[s] e[r]
+ *   J_move    = 1/2 sum_mv du_mv' uwt[s] du_mv
+ * with xa the record's dx_aug after AdjustAllDelayedStates (u_old).  Then
+ *   J_track + J_move - J_track(du = 0) = 1/2 du' H du + (f + G d)' du,
+ * the objective of the QP the step solved.  Limits do not enter.
+ *
+ * cmpc_predict: asynchronous on the ctx stream.  du_device NULL: the
+ * context's current plans (what cmpc_download returns).  du_other_device
+ * NULL: gathered from the other slots of the same scenario, out of the same
+ * array as du (needs nu_tot = S * nu); ignored for nVo = 0.  flags must be 0.
+ * cmpc_predict_host: the same two arrays from host memory (staged as the
+ * other _host calls stage theirs).
+ * Results: y_pred, B*S*p*ny doubles (slot, then horizon row, then output),
+ * and cost, B*S*2 doubles [J_track, J_move]; the two buffers are allocated by
+ * the first cmpc_predict (the pointers are NULL before), so a context that
+ * never predicts allocates nothing for it.  cmpc_download_prediction makes
+ * host copies (either pointer may be NULL); -1 before the first prediction.
+ *
+ * The prediction reads what the build read (records, u_old, weights and
+ * references, dy_ref).  cmpc_predict is refused (-1, the message names the
+ * cause) before a build has run (cmpc_build, or the build inside cmpc_step /
+ * cmpc_control_step) and after any call that changed one of them since:
+ * CMPC_APPLY_MOVE in any call, cmpc_observe_apply, cmpc_update_u[_host],
+ * cmpc_control_step*, cmpc_set_state with u_old, cmpc_bind_state,
+ * cmpc_upload_lin, cmpc_bind_lin, cmpc_produce_lin, cmpc_observe_step*,
+ * cmpc_observer_init*, cmpc_set_weights, cmpc_set_reference,
+ * cmpc_set/bind_scenario_reference.  The flag lives on the host: writes the
+ * library does not see (a producer writing through cmpc_lin_device(), bound
+ * state or offsets changed by the caller's kernels) are the caller's to order.
+ *
+ * cmpc_predict_available: host only, 1 where a predict kernel instance
+ * exists (every dimension set that has a one-QP-per-wave build instance), 0
+ * elsewhere; cmpc_predict fails with a message for other dimensions. */
+int cmpc_predict(cmpc_ctx* ctx, const double* du_device, const double* du_other_device, uint32_t flags);
+int cmpc_predict_host(cmpc_ctx* ctx, const double* du, const double* du_other, uint32_t flags);
+double* cmpc_prediction_device(cmpc_ctx* ctx);
+double* cmpc_prediction_cost_device(cmpc_ctx* ctx);
+int cmpc_download_prediction(cmpc_ctx* ctx, double* y_pred, double* cost);
+int cmpc_predict_available(const cmpc_dims* dims);
+
 /* Per-kernel device time (HIP events stamped by the kernel's own dispatch,
  * opt-in).  enable: 0 off, 1 every kernel, or an OR of CMPC_TIME_ONLY(k)
  * to time only those kernels (the others launch without events). */
