@@ -21,15 +21,15 @@ from ._abi import (CMPC_BUILD_AUTO, CMPC_BUILD_ROWS, CMPC_BUILD_SPLIT, CMPC_BUIL
                    CMPC_APPLY_MOVE, CMPC_KERNEL_BUILD, CMPC_KERNEL_ITERATE,
                    CMPC_KERNEL_PRODUCE, CMPC_KERNEL_OBSERVE_POST, CMPC_KERNEL_OBSERVE_PRIOR, CMPC_QP_INFEASIBLE,
                    CMPC_QP_MAX_NWSR, CMPC_QP_NOT_PD, CMPC_QP_NONFINITE, CMPC_QP_OK, CMPC_TRACE, CmpcDims,
-                   CmpcLayout, CmpcPlan, CMPC_PLAN_DU_OTHER, bptr, check, dptr, iptr, load_library, uptr)
+                   CmpcLayout, CmpcPlan, CMPC_PLAN_DU_OTHER, CMPC_PLAN_REF_PROFILE, bptr, check, dptr, iptr, load_library, uptr)
 from .configs import ControllerConfig, SetupFile, reference_config, reference_observer_gain, reference_setup
 from .problem import ControllerArrays, controller_arrays, plant_input_from_plans
 
 __all__ = ["Context", "ControllerConfig", "SetupFile", "reference_config", "reference_setup",
            "reference_observer_gain", "controller_arrays",
            "plant_input_from_plans", "plant_lin_record", "plant_default", "plant_output",
-           "scenario_reference_offsets", "scenario_limits",
-           "layout_of", "plan", "predict_available", "plan_error_string", "rows_lds_model", "qp_solve_batch", "CMPC_APPLY_MOVE", "CMPC_TRACE", "CMPC_QP_OK",
+           "scenario_reference_offsets", "scenario_reference_profiles", "scenario_limits",
+           "layout_of", "plan", "predict_available", "reference_profile_available", "CMPC_PLAN_REF_PROFILE", "plan_error_string", "rows_lds_model", "qp_solve_batch", "CMPC_APPLY_MOVE", "CMPC_TRACE", "CMPC_QP_OK",
            "CMPC_QP_MAX_NWSR", "CMPC_QP_INFEASIBLE", "CMPC_QP_NOT_PD",
            "CMPC_QP_NONFINITE"]
 
@@ -44,7 +44,7 @@ def plan(dims: CmpcDims, cus: int, build: int = CMPC_BUILD_AUTO, solve: int = CM
          step: int = CMPC_STEP_AUTO, K: int = 1, flags: int = 0) -> CmpcPlan:
     """Which kernels a batch of dims.B scenarios gets on a device of `cus`
     compute units under the three variants, for calls with K iterations
-    and `flags` (CMPC_TRACE, CMPC_PLAN_DU_OTHER): cmpc_plan, the library's own
+    and `flags` (CMPC_TRACE, CMPC_PLAN_DU_OTHER, CMPC_PLAN_REF_PROFILE): cmpc_plan, the library's own
     selection (csrc/dispatch.cpp), answered without a device."""
     out = CmpcPlan()
     check(load_library().cmpc_plan(ctypes.byref(dims), int(cus), int(build), int(solve), int(step), int(K),
@@ -55,6 +55,12 @@ def plan(dims: CmpcDims, cus: int, build: int = CMPC_BUILD_AUTO, solve: int = CM
 def predict_available(dims: CmpcDims) -> bool:
     """Whether Context.predict has a kernel instance for dims (host only)."""
     return bool(load_library().cmpc_predict_available(ctypes.byref(dims)))
+
+
+def reference_profile_available(dims: CmpcDims) -> bool:
+    """Whether Context.set/bind_scenario_reference_profile has a kernel
+    instance for dims (host only)."""
+    return bool(load_library().cmpc_reference_profile_available(ctypes.byref(dims)))
 
 
 def plan_error_string(code: int) -> str:
@@ -157,6 +163,22 @@ def scenario_reference_offsets(cfg: ControllerConfig, y_offset) -> np.ndarray:
         raise ValueError(f"y_offset must be (B, n_outputs) with n_outputs >= {n_out}, got {y_offset.shape}")
     oi = np.asarray(cfg.out_idx, dtype=np.int64)[:, :cfg.ny]      # (S, ny)
     return np.ascontiguousarray(y_offset[:, oi].reshape(y_offset.shape[0] * cfg.S, cfg.ny))
+
+
+def scenario_reference_profiles(cfg: ControllerConfig, y_dev) -> np.ndarray:
+    """Plant-level reference profiles -> slots.  y_dev: (B, p, n_outputs), one
+    deviation per scenario, horizon row and plant output; returns (B*S, p, ny)
+    in slot order q = b*S + s, sub-controller s taking its outputs
+    cfg.out_idx[s] (Context.set_scenario_reference_profile).  The 3-D sibling
+    of scenario_reference_offsets."""
+    y_dev = np.asarray(y_dev, dtype=np.float64)
+    n_out = int(np.max(cfg.out_idx)) + 1
+    if y_dev.ndim != 3 or y_dev.shape[2] < n_out:
+        raise ValueError(f"y_dev must be (B, p, n_outputs) with n_outputs >= {n_out}, got {y_dev.shape}")
+    oi = np.asarray(cfg.out_idx, dtype=np.int64)[:, :cfg.ny]      # (S, ny)
+    B, p = y_dev.shape[:2]
+    # (B, p, S, ny) -> (B, S, p, ny)
+    return np.ascontiguousarray(y_dev[:, :, oi].transpose(0, 2, 1, 3).reshape(B * cfg.S, p, cfg.ny))
 
 
 def scenario_limits(cfg: ControllerConfig, lower, upper, rate_lower, rate_upper):
@@ -289,6 +311,34 @@ class Context:
         """Bind a device-resident (B*S, ny) f64 offset array (0 clears)."""
         check(self.lib.cmpc_bind_scenario_reference(self._h, ctypes.c_void_p(device_ptr or None)),
               "cmpc_bind_scenario_reference")
+
+    def set_scenario_reference_profile(self, dref=None):
+        """Per-slot reference profiles over the horizon, (B*S, p, ny) host array
+        in slot order (scenario_reference_profiles maps plant outputs to
+        slots): slot q tracks y_ref[s][r] + dy_ref[q] + dref[q][r] from the
+        next build on.  None clears."""
+        if dref is None:
+            check(self.lib.cmpc_set_scenario_reference_profile(self._h, None),
+                  "cmpc_set_scenario_reference_profile")
+            return
+        dr = np.ascontiguousarray(dref, np.float64)
+        n = self.nqp * self.cfg.p * self.cfg.ny
+        if dr.size != n:
+            raise ValueError(f"dref must hold B*S*p*ny = {n} values, got {dr.shape}")
+        check(self.lib.cmpc_set_scenario_reference_profile(self._h, dptr(dr)),
+              "cmpc_set_scenario_reference_profile")
+
+    def bind_scenario_reference_profile(self, device_ptr: int = 0):
+        """Bind a device-resident (B*S, p, ny) f64 profile array (0 clears)."""
+        check(self.lib.cmpc_bind_scenario_reference_profile(self._h, ctypes.c_void_p(device_ptr or None)),
+              "cmpc_bind_scenario_reference_profile")
+
+    def get_scenario_reference_profile(self) -> np.ndarray:
+        """(B*S, p, ny): the profile in force (set or bound); raises if none."""
+        out = np.zeros((self.nqp, self.cfg.p, self.cfg.ny))
+        check(self.lib.cmpc_get_scenario_reference_profile(self._h, dptr(out)),
+              "cmpc_get_scenario_reference_profile")
+        return out
 
     def set_scenario_constraints(self, lower=None, upper=None, rate_lower=None, rate_upper=None):
         """Per-slot input limits, four (B*S, nu) host arrays in slot order

@@ -46,6 +46,7 @@ CMPC_STEP_SPLIT = 1
 CMPC_STEP_FUSED = 2
 
 CMPC_PLAN_DU_OTHER = 0x100
+CMPC_PLAN_REF_PROFILE = 0x200
 CMPC_PLAN_OK = 0
 CMPC_PLAN_NO_ROWS_BUILD = 1
 CMPC_PLAN_NO_BUILD = 2
@@ -135,6 +136,8 @@ EXPORTS = (
     "cmpc_sim_set_input_host", "cmpc_sim_set_offset_host", "cmpc_sim_output_host",
     "cmpc_predict", "cmpc_predict_host", "cmpc_prediction_device", "cmpc_prediction_cost_device",
     "cmpc_download_prediction", "cmpc_predict_available",
+    "cmpc_set_scenario_reference_profile", "cmpc_bind_scenario_reference_profile",
+    "cmpc_get_scenario_reference_profile", "cmpc_reference_profile_available",
 )
 
 _lib = None
@@ -266,6 +269,10 @@ def load_library(path: str = LIB_PATH):
         "cmpc_prediction_cost_device": ([c_void], c_void),
         "cmpc_download_prediction": ([c_void, P(dbl), P(dbl)], ctypes.c_int),
         "cmpc_predict_available": ([P(CmpcDims)], ctypes.c_int),
+        "cmpc_set_scenario_reference_profile": ([c_void, P(dbl)], ctypes.c_int),
+        "cmpc_bind_scenario_reference_profile": ([c_void, c_void], ctypes.c_int),
+        "cmpc_get_scenario_reference_profile": ([c_void, P(dbl)], ctypes.c_int),
+        "cmpc_reference_profile_available": ([P(CmpcDims)], ctypes.c_int),
         "cmpc_qp_solve_batch": ([ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(dbl),
                                  P(dbl), P(dbl), P(dbl), P(dbl), P(dbl), P(u32), ctypes.c_int,
                                  P(dbl), P(i32), P(i32), P(u32), P(ctypes.c_uint8), P(i32)],

@@ -79,6 +79,7 @@ class ClosedLoop:
     limits         (lower, upper, rate_lower, rate_upper), each (B, nu_tot) in
                    plant control order: per-scenario input limits, or None
     Both are in force before initialize (the first build and the cold solves).
+    set_setpoint_schedule adds per-scenario setpoint schedules with preview.
     """
 
     def __init__(self, cfg: ControllerConfig, arrays, M, x0, u_offset, K: int, device: int = 0,
@@ -110,6 +111,8 @@ class ClosedLoop:
         self.io = np.ascontiguousarray(cfg.input_order, dtype=np.int32)
         self.k = 0
         self._sched = []   # pending (t_start, plant-input offset (B, n_inputs) device)
+        self._sp_sched = None   # setpoint schedule in slot order, (B, S, T, ny) device
+        self._sp_window = None  # the bound reference profile, (B*S, p, ny) device
 
     def set_segments(self, segments, u_default):
         """The setup file's `simulation` segments ([(offset change, end time)],
@@ -138,6 +141,46 @@ class ClosedLoop:
             raise ValueError(f"y_offset must be (B = {self.B}, n_outputs), got {y_offset.shape}")
         self.ctx.set_scenario_reference(scenario_reference_offsets(self.cfg, y_offset))
 
+    def set_setpoint_schedule(self, schedule):
+        """Per-scenario setpoint schedules with preview: (B, T, n_outputs)
+        plant-output deviations per control step, in force from the next build
+        on; None removes them.  At control step t slot q = b*S + s tracks, at
+        horizon row r, its reference plus
+        schedule[b][min(t + 1 + r, T - 1)][out_idx[s]]: row r is the output
+        1 + r samples after the step's measurement (as the prediction's row 0
+        is the output after the first move), and the schedule's last row is
+        held past its end.  The window is gathered on the device and bound as
+        the context's reference profile
+        (Context.bind_scenario_reference_profile).  Independent of
+        set_setpoints; the two add."""
+        torch = self.torch
+        if schedule is None:
+            self.ctx.bind_scenario_reference_profile(0)
+            self._sp_sched = self._sp_window = None
+            return
+        schedule = np.asarray(schedule, dtype=np.float64)
+        n_out = int(np.max(self.cfg.out_idx)) + 1
+        if schedule.ndim != 3 or schedule.shape[0] != self.B or schedule.shape[1] < 1 or schedule.shape[2] < n_out:
+            raise ValueError(f"schedule must be (B = {self.B}, T >= 1, n_outputs >= {n_out}), got {schedule.shape}")
+        if not np.isfinite(schedule).all():
+            raise ValueError("schedule must be finite")
+        oi = torch.as_tensor(np.asarray(self.cfg.out_idx, dtype=np.int64)[:, :self.cfg.ny], device=self.dev)
+        sch = torch.from_numpy(np.ascontiguousarray(schedule)).to(self.dev)
+        # (B, T, S, ny) -> (B, S, T, ny)
+        self._sp_sched = sch[:, :, oi].permute(0, 2, 1, 3).contiguous()
+        self._sp_window = torch.zeros(self.B * self.cfg.S, self.cfg.p, self.cfg.ny, dtype=torch.float64,
+                                      device=self.dev)
+        self._sp_rows = torch.arange(self.cfg.p, device=self.dev)
+        self.ctx.bind_scenario_reference_profile(self._sp_window.data_ptr())
+
+    def _setpoint_window(self):
+        """The schedule's window of control step self.k into the bound profile."""
+        if self._sp_sched is None:
+            return
+        T = self._sp_sched.shape[2]
+        idx = (self._sp_rows + (self.k + 1)).clamp_(max=T - 1)
+        self._sp_window.copy_(self._sp_sched[:, :, idx, :].reshape(self._sp_window.shape))
+
     def initialize(self, dx_init=None):
         """SimulationSystem(x0, u_offset) + NerveCenter::Initialize(x0, 0,
         u_offset, y(x0), dx_init): the observers' state, the records at x0,
@@ -148,9 +191,10 @@ class ClosedLoop:
         self.ctx.observer_init(self.x0.data_ptr(), self.u_offset.data_ptr(), y0.data_ptr(),
                                dx.data_ptr() if dx_init is not None else 0, Ts=self.Ts,
                                p_in=self.p_in, p_out=self.p_out)
+        self.k = 0
+        self._setpoint_window()
         self.ctx.build()
         self.ctx.init_warmstart()
-        self.k = 0
         self.t_seg, self.seg_step = 0.0, 0   # integrate_const's start time and step count
 
     def step(self, trace: bool = False, predict: bool = False):
@@ -173,6 +217,7 @@ class ClosedLoop:
         # plant's may have stepped, see set_segments)
         self.sim.plant_input_offset(self.u_ctrl, self.u_offset, self.u_lin)
         self.ctx.observe_step(self.u_lin.data_ptr(), y.data_ptr())
+        self._setpoint_window()
         self.ctx.build()
         self.ctx.iterate(self.K, CMPC_TRACE if trace else 0)
         if trace:

@@ -148,6 +148,10 @@ struct cmpc_ctx {
   // use) or bound ones (cmpc_bind_scenario_*)
   const double *sc_dy = nullptr, *sc_limits = nullptr;
   double *own_sc_dy = nullptr, *own_sc_limits = nullptr;
+  // per-slot reference profile (nqp * p * ny) in force, or null; set or bound
+  // in the same way (cmpc_set/bind_scenario_reference_profile)
+  const double* sc_dref = nullptr;
+  double* own_sc_dref = nullptr;
   int32_t *status = nullptr, *nwsr = nullptr, *ntrace = nullptr;
   char* out_block = nullptr;  // du | status | nwsr in one allocation: one D2H for cmpc_download
   bool out_host = false;      // out_block is page-locked host memory the kernels write in place
@@ -186,7 +190,7 @@ struct cmpc_ctx {
   bool bp_ok = false;
   BuildParams bp{};                     // cmpc_dispatch_params; bp_error: its error text
   const char* bp_error = nullptr;
-  cmpc_plan_t plans[8];
+  cmpc_plan_t plans[16];
   unsigned plans_valid = 0;             // bit k: plans[k] holds; cleared by cmpc_set_*_variant
   int last_step_fused = 0;
   // prediction (cmpc_predict): buffers allocated by the first call; pred_stale
@@ -382,11 +386,12 @@ int build_params(cmpc_ctx* c, BuildParams& P) {
 // setting, so a step pays no selection work.  (With bp_error no build kernel
 // is available, and the build calls report that error first.)
 const cmpc_plan_t& plan_of(cmpc_ctx* c, int K, bool trace, bool du_other) {
-  const unsigned k = (K > 0 ? 1u : 0u) | (trace ? 2u : 0u) | (du_other ? 4u : 0u);
+  const bool profile = c->sc_dref != nullptr;  // a reference profile is in force: no fused path
+  const unsigned k = (K > 0 ? 1u : 0u) | (trace ? 2u : 0u) | (du_other ? 4u : 0u) | (profile ? 8u : 0u);
   if (!((c->plans_valid >> k) & 1)) {
     ensure_bp(c);
     c->plans[k] = cmpc_dispatch_plan(c->d, c->L, c->bp, c->build_variant, c->solve_variant, c->step_variant,
-                                     K > 0 ? 1 : 0, trace, du_other);
+                                     K > 0 ? 1 : 0, trace, du_other, profile);
     c->plans_valid |= 1u << k;
   }
   return c->plans[k];
@@ -535,7 +540,7 @@ int cmpc_destroy(cmpc_ctx* c) {
                   c->out_host ? nullptr : c->out_block,
                   c->own_ws ? c->own_ws : c->ws,
                   c->trace, c->ntrace, c->obs, c->d_obsM,
-                  c->stage, c->own_sc_dy, c->own_sc_limits, c->pred_y, c->pred_cost};
+                  c->stage, c->own_sc_dy, c->own_sc_limits, c->own_sc_dref, c->pred_y, c->pred_cost};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -811,6 +816,61 @@ int cmpc_get_scenario_reference(cmpc_ctx* c, double* dy_ref) {
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipMemcpyAsync(dy_ref, c->sc_dy, sizeof(double) * (size_t)c->nqp * c->d.ny, hipMemcpyDeviceToHost,
                          c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// Per-slot reference profiles (include/cmpc.h): set, bind and get as the
+// setpoint offsets above; cmpc_build applies them (refshift.hip).
+static const char* const kStaleProfile =
+    "the reference profile has changed since the build (cmpc_set/bind_scenario_reference_profile)";
+static const char* const kNoProfileKernel =
+    ": reference-profile kernel not instantiated for these dimensions (ns, ny, nu, m)";
+
+int cmpc_set_scenario_reference_profile(cmpc_ctx* c, const double* dref) {
+  if (!c) return fail("null context");
+  if (!dref) {
+    if (c->sc_dref) c->pred_stale = kStaleProfile;
+    c->sc_dref = nullptr;
+    return 0;
+  }
+  if (!cmpc_refshift_instance(c->d, c->L))
+    return fail(std::string("cmpc_set_scenario_reference_profile") + kNoProfileKernel);
+  const size_t per = (size_t)c->d.p * c->d.ny, n = (size_t)c->nqp * per;
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(dref[i]))
+      return fail("cmpc_set_scenario_reference_profile: slot " + std::to_string(i / per) +
+                  ": the profile must be finite");
+  c->pred_stale = kStaleProfile;
+  if (scenario_upload(c, &c->own_sc_dref, dref, n)) return -1;
+  c->sc_dref = c->own_sc_dref;
+  return 0;
+}
+
+int cmpc_bind_scenario_reference_profile(cmpc_ctx* c, const double* dref_device) {
+  if (!c) return fail("null context");
+  if (dref_device) {
+    if (!cmpc_refshift_instance(c->d, c->L))
+      return fail(std::string("cmpc_bind_scenario_reference_profile") + kNoProfileKernel);
+    if (!device_ptr_ok(c, dref_device, sizeof(double) * (size_t)c->nqp * c->d.p * c->d.ny)) {
+      (void)hipGetLastError();  // a failed pointer query is not a later launch's error
+      return fail("cmpc_bind_scenario_reference_profile: not a device allocation of nqp * p * ny doubles on the "
+                  "context's device");
+    }
+    if (reinterpret_cast<uintptr_t>(dref_device) % 8)
+      return fail("cmpc_bind_scenario_reference_profile: misaligned array");
+  }
+  if (c->sc_dref || dref_device) c->pred_stale = kStaleProfile;
+  c->sc_dref = dref_device;
+  return 0;
+}
+
+int cmpc_get_scenario_reference_profile(cmpc_ctx* c, double* dref) {
+  if (!c || !dref) return fail("null argument");
+  if (!c->sc_dref) return fail("cmpc_get_scenario_reference_profile: no reference profile is set");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(dref, c->sc_dref, sizeof(double) * (size_t)c->nqp * c->d.p * c->d.ny,
+                         hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -1675,9 +1735,29 @@ int cmpc_build(cmpc_ctx* c) {
     return plan_mismatch("build");
   if (check_launch("build kernel")) return -1;
   c->last_build = pl.build_kernel;
+  if (tl.end()) return -1;
+  if (c->sc_dref) {  // f -= Su' ywt dref, in place (untimed: no CMPC_KERNEL_* slot of its own)
+    RefshiftParams R;
+    std::memset(&R, 0, sizeof R);
+    R.lin = P.lin;
+    R.cfg = P.cfg;
+    R.dref = c->sc_dref;
+    R.qp = P.qp;
+    R.nqp = P.nqp;
+    R.S = P.S;
+    R.p = P.p;
+    R.rec_len = P.rec_len;
+    R.nobs = P.nobs;
+    R.qp_len = P.qp_len;
+    R.off_A = P.off_A; R.off_B = P.off_B; R.off_C = P.off_C;
+    R.co = P.co;
+    for (int i = 0; i < c->d.nu_tot; ++i) R.delay[i] = c->d.delay[i];
+    if (cmpc_launch_refshift(R, c->d, c->stream)) return plan_mismatch("reference profile");
+    if (check_launch("reference-profile kernel")) return -1;
+  }
   c->pred_built = true;
   c->pred_stale = nullptr;
-  return tl.end();
+  return 0;
 }
 
 // working-set trace buffers for K iterations of every QP (CMPC_TRACE)
@@ -2046,6 +2126,7 @@ int cmpc_predict(cmpc_ctx* c, const double* du, const double* du_other, uint32_t
   P.cfg = c->cfg;
   P.u_old = c->u_old;
   P.dy_ref = c->sc_dy;
+  P.dref = c->sc_dref;
   P.du = du ? du : c->du;  // (page-locked host memory up to CMPC_HOST_OUT_MAX_QP slots: its device address)
   P.d = du_other;
   P.y_pred = c->pred_y;

@@ -201,6 +201,7 @@ struct PredictParams {
   const double* cfg;     // S * co.len
   const double* u_old;   // nqp * nu_tot
   const double* dy_ref;  // nqp * ny per-slot setpoint offsets, or null
+  const double* dref;    // nqp * p * ny per-slot reference profiles (RefshiftParams), or null
   const double* du;      // nqp * nV own plans
   const double* d;       // nqp * nVo other controllers' plans (the Jacobi iteration's order), or
                          // null: gathered from du of the scenario's other slots
@@ -215,6 +216,22 @@ struct PredictParams {
 };
 // one QP per 16-lane row, four per one-wave workgroup; -1: no instance
 int cmpc_launch_predict(const PredictParams& P, const cmpc_dims& d, void* stream);
+
+// Reference-profile correction (refshift.hip): f -= Su' w of
+// every QP slot, w[r] = ywt[s] dref[q][r], in place in the QP buffer right
+// after the build.  Reads the records the build read.
+struct RefshiftParams {
+  const double* lin;     // nqp * rec_len
+  const double* cfg;     // S * co.len
+  const double* dref;    // nqp * p * ny, [slot][horizon row][output]
+  double* qp;            // nqp * qp_len; only f (nV doubles at nV * nV) is read and written
+  int nqp, S, p, rec_len, nobs, qp_len;
+  int off_A, off_B, off_C;
+  CfgOffsets co;
+  int delay[CMPC_MAX_INPUTS];  // per input
+};
+// one QP per 16-lane row, four per one-wave workgroup; -1: no instance
+int cmpc_launch_refshift(const RefshiftParams& P, const cmpc_dims& d, void* stream);
 
 // Standalone batched solver (parity / KKT tests).  G (nqp * n * nvo) and d
 // (nqp * nvo) non-null: the Jacobi iteration's map-form solve with g = f + G d

@@ -300,6 +300,21 @@ extern "C" int cmpc_predict_available(const cmpc_dims* dims) {
   return cmpc_predict_instance(*dims, L) ? 1 : 0;
 }
 
+bool cmpc_refshift_instance(const cmpc_dims& d, const cmpc_layout& L) {
+  if (L.nd != CMPC_DIMS_ND || d.nu_tot != CMPC_DIMS_NUT) return false;
+#define CMPC_REFSHIFT_IS(NS_, NY_, NU_, M_) \
+  if (d.ns == NS_ && d.ny == NY_ && d.nu == NU_ && d.m == M_) return true;
+  CMPC_FOR_BUILD_WAVE(CMPC_REFSHIFT_IS)
+#undef CMPC_REFSHIFT_IS
+  return false;
+}
+
+extern "C" int cmpc_reference_profile_available(const cmpc_dims* dims) {
+  cmpc_layout L;
+  if (cmpc_layout_error(dims, &L) || cmpc_context_dims_error(*dims, L)) return 0;
+  return cmpc_refshift_instance(*dims, L) ? 1 : 0;
+}
+
 // ---------------------------------------------------------------------------
 // the policy
 // ---------------------------------------------------------------------------
@@ -355,7 +370,8 @@ constexpr int kControlSplitQpPerCu = 1;
 }  // namespace
 
 cmpc_plan_t cmpc_dispatch_plan(const cmpc_dims& d, const cmpc_layout& L, const BuildParams& P, int build_variant,
-                               int solve_variant, int step_variant, int K, bool trace, bool du_other) {
+                               int solve_variant, int step_variant, int K, bool trace, bool du_other,
+                               bool ref_profile) {
   const int nqp = P.nqp, cus = P.cus;
   cmpc_plan_t pl;
   std::memset(&pl, 0, sizeof pl);
@@ -399,7 +415,10 @@ cmpc_plan_t cmpc_dispatch_plan(const cmpc_dims& d, const cmpc_layout& L, const B
                          nqp <= kFuseUpToQpPerCu * cus && d.p >= kFuseHorizonMin;
   pl.step_build_kernel = pl.build_kernel;
   pl.step_solve_kernel = pl.solve_kernel;
-  if ((step_variant == CMPC_STEP_FUSED || auto_fuse) && K > 0 && own_plans) {
+  if (ref_profile) {
+    // the correction of f runs between the build and the solve
+    if (step_variant == CMPC_STEP_FUSED) pl.step_error = CMPC_PLAN_PROFILE_NEEDS_SPLIT;
+  } else if ((step_variant == CMPC_STEP_FUSED || auto_fuse) && K > 0 && own_plans) {
     const bool leave_rows_lane = rows_fill && L.nV <= kRowsLaneStepNvMax && step_variant == CMPC_STEP_AUTO;
     int kind = 0, solver = 0;
     if (!rows_fill && (solver = cmpc_step_wave_solver(d, P)))
@@ -418,7 +437,7 @@ cmpc_plan_t cmpc_dispatch_plan(const cmpc_dims& d, const cmpc_layout& L, const B
   // control step: one launch (never traced), else the three calls
   pl.control_build_kernel = pl.step_build_kernel;
   pl.control_solve_kernel = pl.step_solve_kernel;
-  if (K > 0 && step_variant != CMPC_STEP_SPLIT && build_variant == CMPC_BUILD_AUTO &&
+  if (K > 0 && !ref_profile && step_variant != CMPC_STEP_SPLIT && build_variant == CMPC_BUILD_AUTO &&
       solve_variant == CMPC_SOLVE_AUTO && nqp <= kControlQpPerCu * cus && own_plans) {
     const bool split = nqp <= kControlSplitQpPerCu * cus;
     const int grid = split ? std::max(1, (nqp + 1) / 2) : P.grid;
@@ -444,6 +463,9 @@ extern "C" const char* cmpc_plan_error_string(int e) {
     case CMPC_PLAN_NO_ROWS_SOLVE: return "row solve kernel not available for these dimensions (S must divide 4)";
     case CMPC_PLAN_NO_SOLVE: return "solve kernel not instantiated for these dimensions";
     case CMPC_PLAN_NO_FUSED_STEP: return "cmpc_step: no fused step kernel for these dimensions";
+    case CMPC_PLAN_PROFILE_NEEDS_SPLIT:
+      return "cmpc_step: a reference profile is in force (cmpc_set/bind_scenario_reference_profile): its "
+             "correction of f runs between the build and the solve, so CMPC_STEP_FUSED cannot be forced";
   }
   return "unknown plan error";
 }
@@ -461,6 +483,6 @@ const char* cmpc_plan_or_error(const cmpc_dims* dims, int cus, int build_variant
   BuildParams P;
   if (const char* e = cmpc_dispatch_params(*dims, L, dims->B * dims->S, cus, &P)) return e;
   *plan = cmpc_dispatch_plan(*dims, L, P, build_variant, solve_variant, step_variant, K, (flags & CMPC_TRACE) != 0,
-                             (flags & CMPC_PLAN_DU_OTHER) != 0);
+                             (flags & CMPC_PLAN_DU_OTHER) != 0, (flags & CMPC_PLAN_REF_PROFILE) != 0);
   return nullptr;
 }

@@ -51,12 +51,20 @@ bool cmpc_solve_rows_available(int nV, int nu, int nVo, int S, int qp_len, bool 
 // one-QP-per-wave build instance (cmpc_predict_available, cmpc.h, adds the
 // context's dimension checks)
 bool cmpc_predict_instance(const cmpc_dims& d, const cmpc_layout& L);
+// the reference-profile correction (refshift.hip) has an instance: the same
+// column (cmpc_reference_profile_available, cmpc.h, adds the context's
+// dimension checks)
+bool cmpc_refshift_instance(const cmpc_dims& d, const cmpc_layout& L);
 
 // --- the policy ------------------------------------------------------------
 // P: cmpc_dispatch_params of the batch (nqp, cus and the layouts).  K, trace
-// and du_other describe the call (cmpc.h, cmpc_plan).
+// and du_other describe the call (cmpc.h, cmpc_plan).  ref_profile: a
+// per-slot reference profile is in force (CMPC_PLAN_REF_PROFILE): the fused
+// paths keep f in registers and cannot take its correction, so the step is
+// two launches and the control step its three calls.
 cmpc_plan_t cmpc_dispatch_plan(const cmpc_dims& d, const cmpc_layout& L, const BuildParams& P, int build_variant,
-                               int solve_variant, int step_variant, int K, bool trace, bool du_other);
+                               int solve_variant, int step_variant, int K, bool trace, bool du_other,
+                               bool ref_profile = false);
 // cmpc_plan (cmpc.h) without the error slot: nullptr, or the error text
 const char* cmpc_plan_or_error(const cmpc_dims* dims, int cus, int build_variant, int solve_variant,
                                int step_variant, int K, uint32_t flags, cmpc_plan_t* plan);

@@ -17,7 +17,8 @@
 // The horizon runs in chunks of 16 steps: lane t fetches the four inputs of
 // step k0 + t, step t takes them by row_newbcast:t; the chunk's outputs go to
 // LDS, from where the row's lanes store them in 128-byte pieces and add up
-// J_track = 1/2 sum |L_W' (y - dy_ref) - yhat|^2, one step per lane.
+// J_track = 1/2 sum |L_W' (y - dy_ref - dref) - yhat|^2, one step per lane
+// (dref: the slot's reference profile where one is in force).
 #include "cmpc_internal.h"
 #include "dispatch.h"
 #include "dpp_blocks.inc"
@@ -155,6 +156,10 @@ __global__ __launch_bounds__(64) void cmpc_predict_kernel(PredictParams P) {
       double e[NY];
 #pragma unroll
       for (int j = 0; j < NY; ++j) e[j] = ybuf[row][lane * NY + j] - dy[j];
+      if (P.dref) {  // the slot's reference profile
+#pragma unroll
+        for (int j = 0; j < NY; ++j) e[j] -= P.dref[((size_t)q * P.p + k) * NY + j];
+      }
 #pragma unroll
       for (int i = 0; i < NY; ++i) {
         double r = -yhat[(size_t)k * NY + i];

@@ -165,8 +165,8 @@ int cmpc_bind_lin(cmpc_ctx* ctx, const double* lin_device);
  * limit vectors (nu values each).  Slot q then tracks y_ref[s][r] + dy_ref[q]
  * at every horizon row r, inside its own lower/upper/rate limits.  Shared by
  * the batch as before: the weights (cmpc_set_weights) and the reference's
- * shape over the horizon (cmpc_set_reference); a reference that differs
- * between scenarios in more than a constant is not expressible here.
+ * base shape over the horizon (cmpc_set_reference).  A reference that differs
+ * between scenarios in more than a constant is a reference profile (below).
  *
  * The offset is applied in the build kernels as y_prev - dy_ref: the reference
  * enters the free response only as kappa - L_W' y_ref with kappa = C_dist
@@ -199,6 +199,50 @@ int cmpc_bind_scenario_constraints(cmpc_ctx* ctx, const double* limits_device /*
 int cmpc_get_scenario_reference(cmpc_ctx* ctx, double* dy_ref);
 int cmpc_get_scenario_constraints(cmpc_ctx* ctx, double* lower, double* upper, double* rate_lower,
                                   double* rate_upper);
+
+/* Per-scenario reference profiles over the horizon (slot order q = b*S + s).
+ *
+ * dref[q][r][o], B*S*p*ny doubles (slot, then horizon row, then output: the
+ * layout of cmpc_predict's y_pred, so one run's prediction can be another's
+ * target).  With a profile in force slot q tracks
+ *   y_ref[s][r] + dy_ref[q] + dref[q][r]
+ * at horizon row r: the profile adds to the constant offset of
+ * cmpc_set_scenario_reference, it does not replace it.  Setpoint steps or
+ * ramps scheduled at different times in different scenarios, and changes the
+ * controller sees coming inside its horizon (preview), are profiles.
+ *
+ * H and G do not depend on the reference and f is affine in it: the profile
+ * changes the QP only by f <- f - Su' w, w[r] = ywt[s] dref[q][r].  cmpc_build
+ * launches a correction kernel (refshift.hip) right after its build kernel,
+ * on the same stream: a backward sweep over the slot's record that never
+ * forms Su, and one FP64 subtraction per entry of f in place; H and G are
+ * neither read nor written.  cmpc_download_qp, cmpc_iterate,
+ * cmpc_init_warmstart, cmpc_get_input and cmpc_coupled_iterate therefore see
+ * the corrected f.  Like dy_ref it takes effect at the next build.  The
+ * correction has no timing slot: cmpc_kernel_time(CMPC_KERNEL_BUILD) stays
+ * the build kernel's own time.
+ *
+ * The fused paths keep f in registers and cannot take the correction.  With
+ * a profile in force cmpc_step runs as cmpc_build + cmpc_iterate (the same
+ * results bit for bit; cmpc_last_step_fused() == 0), CMPC_STEP_FUSED forced
+ * fails (CMPC_PLAN_PROFILE_NEEDS_SPLIT), and cmpc_control_step* runs as its
+ * three calls.  cmpc_plan answers for this case under CMPC_PLAN_REF_PROFILE.
+ * cmpc_predict honours the profile (e[r] below), so its identity keeps
+ * holding.  With nothing set (the default, and the state after a clear) every
+ * call computes exactly what it did without a profile.
+ *
+ * set / bind / get as for cmpc_*_scenario_reference: set validates (every
+ * value finite; the message names the first bad slot) and copies on the ctx
+ * stream into a buffer allocated on first use, NULL clears; bind is checked
+ * as cmpc_bind_state checks its pointers, for B*S*p*ny doubles, 8-byte
+ * aligned, NULL clears; get returns -1 if nothing is in force.  set and bind
+ * fail with a message where the dimensions have no kernel instance
+ * (cmpc_reference_profile_available: host only, 1 for every dimension set
+ * with a one-QP-per-wave build instance, 0 elsewhere). */
+int cmpc_set_scenario_reference_profile(cmpc_ctx* ctx, const double* dref /* B*S*p*ny */);
+int cmpc_bind_scenario_reference_profile(cmpc_ctx* ctx, const double* dref_device /* B*S*p*ny */);
+int cmpc_get_scenario_reference_profile(cmpc_ctx* ctx, double* dref);
+int cmpc_reference_profile_available(const cmpc_dims* dims);
 
 /* Hot path. */
 int cmpc_build(cmpc_ctx* ctx);
@@ -266,9 +310,13 @@ int cmpc_last_step_fused(cmpc_ctx* ctx);
  * context): the plan of cmpc_dispatch_plan for a batch of dims->B scenarios
  * on a device of `cus` compute units under the three variants, for calls
  * with K iterations and `flags` (CMPC_TRACE; CMPC_PLAN_DU_OTHER: the solve is
- * a cmpc_get_input with the other controllers' plans given).  A context
- * takes the same plan with its device's CU count. */
+ * a cmpc_get_input with the other controllers' plans given;
+ * CMPC_PLAN_REF_PROFILE: a reference profile is in force, so no path is
+ * fused: step_fused, control_fused, control_grid and control_polled are 0 and
+ * the step's kernels are those of CMPC_STEP_SPLIT).  A context takes the same
+ * plan with its device's CU count. */
 #define CMPC_PLAN_DU_OTHER 0x100u
+#define CMPC_PLAN_REF_PROFILE 0x200u
 /* plan errors: what a call fails with (cmpc_plan_error_string) */
 #define CMPC_PLAN_OK 0
 #define CMPC_PLAN_NO_ROWS_BUILD 1  /* CMPC_BUILD_ROWS forced, not available */
@@ -276,6 +324,7 @@ int cmpc_last_step_fused(cmpc_ctx* ctx);
 #define CMPC_PLAN_NO_ROWS_SOLVE 3  /* CMPC_SOLVE_ROWS forced, not available */
 #define CMPC_PLAN_NO_SOLVE 4       /* no solve kernel instance for (nV, nu, nVo) */
 #define CMPC_PLAN_NO_FUSED_STEP 5  /* CMPC_STEP_FUSED forced, not available */
+#define CMPC_PLAN_PROFILE_NEEDS_SPLIT 6  /* CMPC_STEP_FUSED forced with a reference profile in force */
 typedef struct cmpc_plan_t {
   /* cmpc_build */
   int32_t build_kernel;        /* CMPC_BUILD_WAVE / ROWS / SPLIT; 0 with build_error */
@@ -288,7 +337,7 @@ typedef struct cmpc_plan_t {
    * after it */
   int32_t step_fused;
   int32_t step_build_kernel, step_solve_kernel;
-  int32_t step_error;          /* CMPC_PLAN_NO_FUSED_STEP or 0 */
+  int32_t step_error;          /* CMPC_PLAN_NO_FUSED_STEP, CMPC_PLAN_PROFILE_NEEDS_SPLIT or 0 */
   /* cmpc_control_step: one launch, or the three calls with cmpc_step as above */
   int32_t control_fused;
   int32_t control_build_kernel, control_solve_kernel;
@@ -330,7 +379,7 @@ int cmpc_download_trace(cmpc_ctx* ctx, uint8_t* trace, int32_t* ntrace);
  * the Jacobi iteration's order d[mv*nuo + rank*nu + c], rank = index among the
  * scenario's other sub-controllers):
  *   y_pred[r] = y_prev + (Su du + Su_other d + Sf fd + Sx xa)[r],  r = 0..p-1
- *   e[r]      = y_pred[r] - (y_ref[s][r] + dy_ref[q])
+ *   e[r]      = y_pred[r] - (y_ref[s][r] + dy_ref[q] + dref[q][r])
  *   J_track   = 1/2 sum_r e[r]' ywt[s] e[r]
  *   J_move    = 1/2 sum_mv du_mv' uwt[s] du_mv
  * with xa the record's dx_aug after AdjustAllDelayedStates (u_old).  Then
@@ -357,7 +406,8 @@ int cmpc_download_trace(cmpc_ctx* ctx, uint8_t* trace, int32_t* ntrace);
  * cmpc_control_step*, cmpc_set_state with u_old, cmpc_bind_state,
  * cmpc_upload_lin, cmpc_bind_lin, cmpc_produce_lin, cmpc_observe_step*,
  * cmpc_observer_init*, cmpc_set_weights, cmpc_set_reference,
- * cmpc_set/bind_scenario_reference.  The flag lives on the host: writes the
+ * cmpc_set/bind_scenario_reference, cmpc_set/bind_scenario_reference_profile.
+ * The flag lives on the host: writes the
  * library does not see (a producer writing through cmpc_lin_device(), bound
  * state or offsets changed by the caller's kernels) are the caller's to order.
  *
