@@ -16,7 +16,8 @@ import ctypes
 import numpy as np
 
 from . import _abi
-from ._abi import (CMPC_BUILD_AUTO, CMPC_BUILD_ROWS, CMPC_BUILD_SPLIT, CMPC_BUILD_WAVE, CMPC_SOLVE_AUTO, CMPC_SOLVE_LANE,
+from ._abi import (CMPC_BUILD_AUTO, CMPC_BUILD_ROWS, CMPC_BUILD_SPLIT, CMPC_BUILD_WAVE, CMPC_PAIRING_AUTO,
+                   CMPC_PAIRING_OFF, CMPC_PAIRING_ON, CMPC_SOLVE_AUTO, CMPC_SOLVE_LANE,
                    CMPC_SOLVE_ROWS, CMPC_STEP_AUTO, CMPC_STEP_FUSED, CMPC_STEP_SPLIT, CMPC_KERNEL_STEP,
                    CMPC_APPLY_MOVE, CMPC_KERNEL_BUILD, CMPC_KERNEL_ITERATE,
                    CMPC_KERNEL_PRODUCE, CMPC_KERNEL_OBSERVE_POST, CMPC_KERNEL_OBSERVE_PRIOR, CMPC_QP_INFEASIBLE,
@@ -31,7 +32,8 @@ __all__ = ["Context", "ControllerConfig", "SetupFile", "reference_config", "refe
            "scenario_reference_offsets", "scenario_reference_profiles", "scenario_limits",
            "layout_of", "plan", "predict_available", "reference_profile_available", "CMPC_PLAN_REF_PROFILE", "plan_error_string", "rows_lds_model", "qp_solve_batch", "CMPC_APPLY_MOVE", "CMPC_TRACE", "CMPC_QP_OK",
            "CMPC_QP_MAX_NWSR", "CMPC_QP_INFEASIBLE", "CMPC_QP_NOT_PD",
-           "CMPC_QP_NONFINITE"]
+           "CMPC_QP_NONFINITE", "build_pairing_available", "build_pairing_reason", "CMPC_PAIRING_AUTO",
+           "CMPC_PAIRING_OFF", "CMPC_PAIRING_ON"]
 
 
 def layout_of(dims: CmpcDims) -> CmpcLayout:
@@ -61,6 +63,37 @@ def reference_profile_available(dims: CmpcDims) -> bool:
     """Whether Context.set/bind_scenario_reference_profile has a kernel
     instance for dims (host only)."""
     return bool(load_library().cmpc_reference_profile_available(ctypes.byref(dims)))
+
+
+def _lwt_pair(dims: CmpcDims, lwt_s0, lwt_s1):
+    if lwt_s0 is None or lwt_s1 is None:
+        return None, None, None
+    n = dims.ny * dims.ny
+    a = np.ascontiguousarray(lwt_s0, dtype=np.float64).reshape(-1)
+    b = np.ascontiguousarray(lwt_s1, dtype=np.float64).reshape(-1)
+    if a.size != n or b.size != n:
+        raise ValueError("lwt tables must be ny x ny")
+    dp = ctypes.POINTER(ctypes.c_double)
+    return (a, b), a.ctypes.data_as(dp), b.ctypes.data_as(dp)
+
+
+def build_pairing_reason(dims: CmpcDims, lwt_s0=None, lwt_s1=None) -> str:
+    """Why Context.set_build_pairing(CMPC_PAIRING_ON) would refuse dims (host
+    only): "" when the shared form of the row build is eligible.  lwt_s0 /
+    lwt_s1: the two sub-controllers' L_W' tables (ny x ny), compared bit for
+    bit; None leaves the weights out."""
+    keep, pa, pb = _lwt_pair(dims, lwt_s0, lwt_s1)
+    out = load_library().cmpc_build_pairing_reason(ctypes.byref(dims), pa, pb)
+    del keep
+    return out.decode()
+
+
+def build_pairing_available(dims: CmpcDims, lwt_s0=None, lwt_s1=None) -> bool:
+    """Whether the shared form of the row build is eligible for dims (host only)."""
+    keep, pa, pb = _lwt_pair(dims, lwt_s0, lwt_s1)
+    out = bool(load_library().cmpc_build_pairing_available(ctypes.byref(dims), pa, pb))
+    del keep
+    return out
 
 
 def plan_error_string(code: int) -> str:
@@ -464,6 +497,19 @@ class Context:
         (four QPs per wave, one per DPP row) / CMPC_BUILD_SPLIT (one QP per two
         waves: chain and gather, every ny)."""
         check(self.lib.cmpc_set_build_variant(self._h, int(variant)), "cmpc_set_build_variant")
+
+    def set_build_pairing(self, mode: int):
+        """CMPC_PAIRING_AUTO / CMPC_PAIRING_OFF / CMPC_PAIRING_ON: whether the row
+        build shares the Markov chain between a cooperative scenario's two QPs
+        (cmpc.h).  ON raises where the configuration is not eligible."""
+        check(self.lib.cmpc_set_build_pairing(self._h, int(mode)), "cmpc_set_build_pairing")
+
+    def last_build_shared_scenarios(self) -> int:
+        """Scenarios the last build() built in the shared form, -1 if that build
+        was not the shared form."""
+        v = self.lib.cmpc_last_build_shared_scenarios(self._h)
+        check(min(v + 1, 0), "cmpc_last_build_shared_scenarios")
+        return v
 
     def last_build_kernel(self) -> int:
         """CMPC_BUILD_WAVE / CMPC_BUILD_ROWS / CMPC_BUILD_SPLIT: the kernel the

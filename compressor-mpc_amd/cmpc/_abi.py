@@ -38,6 +38,9 @@ CMPC_BUILD_AUTO = 0
 CMPC_BUILD_WAVE = 1
 CMPC_BUILD_ROWS = 2
 CMPC_BUILD_SPLIT = 3
+CMPC_PAIRING_AUTO = 0
+CMPC_PAIRING_OFF = 1
+CMPC_PAIRING_ON = 2
 CMPC_SOLVE_AUTO = 0
 CMPC_SOLVE_LANE = 1
 CMPC_SOLVE_ROWS = 2
@@ -138,6 +141,8 @@ EXPORTS = (
     "cmpc_download_prediction", "cmpc_predict_available",
     "cmpc_set_scenario_reference_profile", "cmpc_bind_scenario_reference_profile",
     "cmpc_get_scenario_reference_profile", "cmpc_reference_profile_available",
+    "cmpc_set_build_pairing", "cmpc_build_pairing_available", "cmpc_build_pairing_reason",
+    "cmpc_last_build_shared_scenarios",
 )
 
 _lib = None
@@ -273,6 +278,10 @@ def load_library(path: str = LIB_PATH):
         "cmpc_bind_scenario_reference_profile": ([c_void, c_void], ctypes.c_int),
         "cmpc_get_scenario_reference_profile": ([c_void, P(dbl)], ctypes.c_int),
         "cmpc_reference_profile_available": ([P(CmpcDims)], ctypes.c_int),
+        "cmpc_set_build_pairing": ([c_void, ctypes.c_int], ctypes.c_int),
+        "cmpc_build_pairing_available": ([P(CmpcDims), P(dbl), P(dbl)], ctypes.c_int),
+        "cmpc_build_pairing_reason": ([P(CmpcDims), P(dbl), P(dbl)], ctypes.c_char_p),
+        "cmpc_last_build_shared_scenarios": ([c_void], ctypes.c_int),
         "cmpc_qp_solve_batch": ([ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(dbl),
                                  P(dbl), P(dbl), P(dbl), P(dbl), P(dbl), P(u32), ctypes.c_int,
                                  P(dbl), P(i32), P(i32), P(u32), P(ctypes.c_uint8), P(i32)],

@@ -17,6 +17,7 @@
 
 int cmpc_launch_build_rows(const BuildParams& P, const cmpc_dims& d, void* stream) {
   hipStream_t s = (hipStream_t)stream;
+  if (P.use_pair) return cmpc_launch_build_pair(P, d, stream);  // the shared form (cmpc_set_build_pairing)
   const int w = cmpc_build_rows_waves(d, P);  // 4 or 2
   if (!w) return -1;
   const bool ring = rows_has_ring(P.rows);

@@ -178,6 +178,13 @@ struct cmpc_ctx {
   // build kernel selection (cmpc_set_build_variant)
   int build_variant = CMPC_BUILD_AUTO;
   int last_build = 0;  // kernel launched by the last cmpc_build
+  // build pairing (cmpc_set_build_pairing): the mode; two coverage counters
+  // used alternately by the shared-form launches (each launch clears the next
+  // one's, so no launch needs a memset); whether the last build was shared
+  int pairing = CMPC_PAIRING_AUTO;
+  uint32_t* pair_cnt = nullptr;
+  unsigned pair_seq = 0;
+  bool last_pair = false;
   int solve_variant = CMPC_SOLVE_AUTO;  // cmpc_set_solve_variant
   int last_solve = 0;                   // kernel launched by the last solve
   int step_variant = CMPC_STEP_AUTO;    // cmpc_set_step_variant
@@ -540,7 +547,8 @@ int cmpc_destroy(cmpc_ctx* c) {
                   c->out_host ? nullptr : c->out_block,
                   c->own_ws ? c->own_ws : c->ws,
                   c->trace, c->ntrace, c->obs, c->d_obsM,
-                  c->stage, c->own_sc_dy, c->own_sc_limits, c->own_sc_dref, c->pred_y, c->pred_cost};
+                  c->stage, c->own_sc_dy, c->own_sc_limits, c->own_sc_dref, c->pred_y, c->pred_cost,
+                  c->pair_cnt};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -1202,6 +1210,7 @@ static int control_step(cmpc_ctx* c, const double* u_full, const double* y, int 
   if (cmpc_launch_control_step(C, c->d, c->stream)) return plan_mismatch("control step");
   if (check_launch("control step kernel")) return -1;
   c->last_build = pl.control_build_kernel;
+  c->last_pair = false;
   c->last_solve = pl.control_solve_kernel;
   c->last_step_fused = 1;
   c->pred_built = true;  // (and stale at once: the a-priori phase has moved u_old)
@@ -1719,6 +1728,42 @@ int cmpc_last_build_kernel(cmpc_ctx* c) {
   return c->last_build;
 }
 
+int cmpc_set_build_pairing(cmpc_ctx* c, int mode) {
+  if (!c) return fail("null context");
+  if (mode != CMPC_PAIRING_AUTO && mode != CMPC_PAIRING_OFF && mode != CMPC_PAIRING_ON)
+    return fail("cmpc_set_build_pairing: unknown mode");
+  if (mode == CMPC_PAIRING_ON) {  // the dimensions' part now; the weights when a build has them
+    ensure_bp(c);
+    if (c->bp_error) return fail(c->bp_error);
+    if (const char* e = cmpc_pairing_error(c->d, c->bp, nullptr, nullptr))
+      return fail(std::string("cmpc_set_build_pairing: ") + e);
+  }
+  c->pairing = mode;
+  return 0;
+}
+
+int cmpc_last_build_shared_scenarios(cmpc_ctx* c) {
+  if (!c) return fail("null context") - 1;
+  if (!c->last_pair || !c->pair_cnt) return -1;
+  if (hipSetDevice(c->device) != hipSuccess) return fail("hipSetDevice") - 1;
+  uint32_t v = 0;
+  if (hipMemcpyAsync(&v, c->pair_cnt + ((c->pair_seq - 1) & 1u), sizeof v, hipMemcpyDeviceToHost, c->stream) !=
+          hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return fail("cmpc_last_build_shared_scenarios: reading the counter failed") - 1;
+  return (int)v;
+}
+
+// whether this cmpc_build runs the shared form of the row build; <0: an error
+static int build_uses_pairing(cmpc_ctx* c, const BuildParams& P, const cmpc_plan_t& pl) {
+  if (c->pairing == CMPC_PAIRING_OFF || pl.build_kernel != CMPC_BUILD_ROWS) return 0;
+  const double* lw0 = c->h_cfg.data() + c->co.lwt;
+  const double* lw1 = c->d.S > 1 ? lw0 + c->co.len : lw0;
+  const char* e = cmpc_pairing_error(c->d, P, lw0, lw1);
+  if (c->pairing == CMPC_PAIRING_ON) return e ? fail(std::string("cmpc_build (CMPC_PAIRING_ON): ") + e) : 1;
+  return !e && cmpc_pairing_auto(c->d.B) ? 1 : 0;
+}
+
 int cmpc_build(cmpc_ctx* c) {
   if (!c) return fail("null context");
   if (ensure_cfg(c)) return -1;
@@ -1727,6 +1772,17 @@ int cmpc_build(cmpc_ctx* c) {
   if (build_params(c, P)) return -1;
   const cmpc_plan_t& pl = plan_of(c, 0, false, false);
   if (pl.build_error) return fail(cmpc_plan_error_string(pl.build_error));
+  const int pair = build_uses_pairing(c, P, pl);
+  if (pair < 0) return -1;
+  if (pair) {
+    if (!c->pair_cnt) {
+      HIP_TRY(hipMalloc(&c->pair_cnt, 2 * sizeof(uint32_t)));
+      HIP_TRY(hipMemsetAsync(c->pair_cnt, 0, 2 * sizeof(uint32_t), c->stream));
+    }
+    P.use_pair = 1;
+    P.pair_cnt = c->pair_cnt + (c->pair_seq & 1u);
+    P.pair_cnt_next = c->pair_cnt + ((c->pair_seq + 1) & 1u);
+  }
   TimedLaunch tl(c, CMPC_KERNEL_BUILD);
   if (tl.begin()) return -1;
   P.split = pl.build_kernel == CMPC_BUILD_SPLIT;
@@ -1734,6 +1790,8 @@ int cmpc_build(cmpc_ctx* c) {
                                          : cmpc_launch_build(P, c->d, c->stream))
     return plan_mismatch("build");
   if (check_launch("build kernel")) return -1;
+  if (pair) ++c->pair_seq;
+  c->last_pair = pair != 0;
   c->last_build = pl.build_kernel;
   if (tl.end()) return -1;
   if (c->sc_dref) {  // f -= Su' ywt dref, in place (untimed: no CMPC_KERNEL_* slot of its own)
@@ -2031,6 +2089,7 @@ int cmpc_step(cmpc_ctx* c, int K, uint32_t flags) {
     return plan_mismatch("fused step");
   if (check_launch("fused step kernel")) return -1;
   c->last_build = pl.step_build_kernel;
+  c->last_pair = false;
   c->last_solve = pl.step_solve_kernel;
   c->last_step_fused = 1;
   c->pred_built = true;

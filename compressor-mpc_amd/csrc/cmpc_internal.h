@@ -133,6 +133,18 @@ struct RowsLayout {
   int U;                          // the kernel's horizon unroll (cmpc_rows_unroll)
 };
 
+// Shared-form row build (build_pair_kernel.h): one cooperative scenario per
+// row.  Its wave region keeps RowsLayout's hand-off areas and C_hat rows and
+// adds: [z of slot 1: 4 x U x NY at z1_off][w: 4 x 2 x ND x WL at w_off].  The
+// group's staging, 4 x (rec_len + rec_len - tail0) doubles, overlays the
+// region up to w_off: the w tables are filled while the records are read.
+#define CMPC_PAIR_CMP 4          // 64-entry blocks of a record's head (A, B, C, f) compared per lane
+struct PairLayout {
+  int ok;                        // the shared form can run these dimensions
+  int z1_off, w_off, WL, per_wave;
+  int tail0;                     // first entry (even) of the other slot's staged tail: off_x rounded down
+};
+
 struct SolveParams {
   const double* qp;
   const double* cfg;
@@ -186,6 +198,13 @@ struct BuildParams {
   int split;                     // cmpc_launch_build: the role-split kernel (every ny)
   int cus;                       // compute units of the device
   RowsLayout rows;               // row-layout kernel (four QPs per wave)
+  // shared form of the row build (cmpc_set_build_pairing): its layout, whether
+  // this launch uses it, and the coverage counters (scenarios built shared):
+  // this launch's and the one it clears for the next launch
+  PairLayout pair;
+  int use_pair;
+  uint32_t* pair_cnt;
+  uint32_t* pair_cnt_next;
   // fused step (cmpc_step on small batches): the K Jacobi iterations run in
   // the build kernel on the QPs it just built (solve_rows.h), with these
   // parameters (sv.qp unused: H, f, G stay in registers)
@@ -358,6 +377,11 @@ int cmpc_rows_resident_groups(const RowsLayout& R, int w);
 // LDS layout of the row kernel, chosen by a bank-conflict model of its
 // horizon loop (rows_layout.cpp); cached per dimension set, thread-safe.
 void cmpc_rows_layout(const cmpc_dims& d, int nd, int nobs, int rec_len, RowsLayout* out);
+// the shared form's wave region on top of the row layout (rows_layout.cpp)
+void cmpc_pair_layout(const cmpc_dims& d, const RowsLayout& R, int nd, int rec_len, int off_x, PairLayout* out);
+// Shared form of the row build (build_pair.hip), launched by
+// cmpc_launch_build_rows when P.use_pair is set; -1: no instance
+int cmpc_launch_build_pair(const BuildParams& P, const cmpc_dims& d, void* stream);
 // modelled extra LDS cycles per wave-step of the horizon loop for one wave
 double cmpc_rows_layout_conflicts(const cmpc_dims& d, int nd, const RowsLayout& R, int wave);
 int cmpc_launch_solve(const SolveParams& P, int nV, int nu, int nVo,

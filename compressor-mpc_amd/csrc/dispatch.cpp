@@ -182,6 +182,7 @@ const char* cmpc_dispatch_params(const cmpc_dims& d, const cmpc_layout& L, int n
   if (sizeof(double) * ((size_t)P.lds_block + (size_t)P.lds_per_wave * CMPC_BUILD_WAVES) > kLdsLimitBytes)
     return "horizon/delays too long for the build kernel's LDS";
   cmpc_rows_layout(d, L.nd, L.nobs, L.rec_len, &P.rows);  // cached per dimension set
+  cmpc_pair_layout(d, P.rows, L.nd, L.rec_len, L.off_x, &P.pair);
   return nullptr;
 }
 
@@ -237,6 +238,65 @@ int cmpc_build_rows_waves(const cmpc_dims& d, const BuildParams& P) {
   if (!rows_layout_usable(P.rows) || !in_build_rows(d, P)) return 0;
   const int w = cmpc_rows_waves_per_group(P.rows);
   return (w == 4 || w == 2) && rows_lds_fits(P.rows, w) ? w : 0;
+}
+
+// CMPC_PAIRING_AUTO: the shared form from this many scenarios on.  It runs
+// half the waves of the unpaired row build at two per SIMD instead of three,
+// so it needs several groups per wave to gain (par-coop, row build forced,
+// unpaired vs shared, three alternating rounds of 30 builds,
+// profiles/pair_build_ab/sizes.txt): 4 096 scenarios (config 2's size) p = 50
+// 25.0-26.1 vs 35.7-36.7 us and p = 20 14.8-15.3 vs 26.8-27.2 us, a loss: one
+// group per SIMD; 16 384 scenarios 77.0-84.2 vs 76.7-80.0 us, level; 32 768
+// scenarios 140-157 vs 128-138 us, the shared form ahead in every round;
+// 65 536 (the headline) 268-315 vs 233-270 us, 0.87x in every round (in the
+// bench's step loop 248 vs 224 us, profiles/pair_build_ab/README.md).
+constexpr int kPairAutoScenarios = 32768;
+
+// Shared form of the row build (build_pair_kernel.h): the two QPs of a
+// cooperative scenario share one P chain.  What must hold per configuration;
+// per scenario the kernel compares the two records' plants bit for bit and
+// builds a group that differs the long way.
+const char* cmpc_pairing_error(const cmpc_dims& d, const BuildParams& P, const double* lwt0, const double* lwt1) {
+  if (d.S != 2 || d.nu_tot != 2 * d.nu)
+    return "build pairing needs two sub-controllers that own half of the inputs each (S = 2, nu_tot = 2 nu)";
+  for (int c = 0; c < d.nu_tot; ++c)
+    if (d.delay[c] != d.delay[(c + d.nu) % d.nu_tot])
+      return "build pairing: the input delays are not invariant under the rotation by nu (the sub-controllers' "
+             "column orders)";
+  if (lwt0 && lwt1 && std::memcmp(lwt0, lwt1, sizeof(double) * d.ny * d.ny) != 0)
+    return "build pairing: the sub-controllers' output weights (lwt) are not bitwise equal";
+  bool inst = false;
+#define CMPC_PAIR_IS(NS_, NY_, NU_, M_) inst = inst || (d.ns == NS_ && d.ny == NY_ && d.nu == NU_ && d.m == M_);
+  CMPC_FOR_BUILD_PAIR(CMPC_PAIR_IS)
+#undef CMPC_PAIR_IS
+  if (!inst || P.nd != CMPC_DIMS_ND || P.nu_tot != CMPC_DIMS_NUT)
+    return "build pairing: no shared-form instance for these dimensions (ns, ny, nu, m; parallel coop only)";
+  if (!cmpc_build_rows_available(d, P)) return "build pairing: the row build cannot run these dimensions";
+  if (rows_has_ring(P.rows)) return "build pairing: the horizon needs ring hand-off lines (no ring instance)";
+  if (!P.pair.ok)
+    return "build pairing: the shared form's LDS region does not fit two workgroups per CU for this horizon";
+  return nullptr;
+}
+
+bool cmpc_pairing_auto(int scenarios) { return scenarios >= kPairAutoScenarios; }
+
+static const char* pairing_reason(const cmpc_dims* dims, const double* lwt0, const double* lwt1) {
+  if (!dims) return "null argument";
+  cmpc_layout L;
+  if (const char* e = cmpc_layout_error(dims, &L)) return e;
+  if (const char* e = cmpc_context_dims_error(*dims, L)) return e;
+  BuildParams P;
+  if (const char* e = cmpc_dispatch_params(*dims, L, dims->B * dims->S, kCusFallback, &P)) return e;
+  return cmpc_pairing_error(*dims, P, lwt0, lwt1);
+}
+
+extern "C" const char* cmpc_build_pairing_reason(const cmpc_dims* dims, const double* lwt_s0, const double* lwt_s1) {
+  const char* e = pairing_reason(dims, lwt_s0, lwt_s1);
+  return e ? e : "";
+}
+
+extern "C" int cmpc_build_pairing_available(const cmpc_dims* dims, const double* lwt_s0, const double* lwt_s1) {
+  return pairing_reason(dims, lwt_s0, lwt_s1) ? 0 : 1;
 }
 
 int cmpc_step_wave_solver(const cmpc_dims& d, const BuildParams& P) {

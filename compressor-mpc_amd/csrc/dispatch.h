@@ -39,6 +39,12 @@ int cmpc_build_rows_waves(const cmpc_dims& d, const BuildParams& P);
 inline bool cmpc_build_rows_available(const cmpc_dims& d, const BuildParams& P) {
   return cmpc_build_rows_waves(d, P) != 0;
 }
+// Shared form of the row build (cmpc_set_build_pairing): nullptr, or why the
+// configuration cannot use it.  lwt0 / lwt1: the two sub-controllers' L_W'
+// tables (ny x ny), compared bit for bit; null: not compared.
+const char* cmpc_pairing_error(const cmpc_dims& d, const BuildParams& P, const double* lwt0, const double* lwt1);
+// CMPC_PAIRING_AUTO uses the shared form for a batch of this many scenarios
+bool cmpc_pairing_auto(int scenarios);
 // fused steps and the one-launch control step: the solver the kernel runs
 // (CMPC_SOLVE_ROWS / CMPC_SOLVE_LANE), 0 when it cannot run
 int cmpc_step_wave_solver(const cmpc_dims& d, const BuildParams& P);

@@ -12,6 +12,11 @@ kernel (build_rows.hip; one QP per 16-lane DPP row, four QPs per wave).
       acc[a] += bcast_{L_a}(cv[o]) * cv[o]   for o < NY, a < NU*M,
       L_a = (a / NU) * NUT + a % NU   (gather lane of own QP column a)
 
+  rows_pair_head / rows_pair_part<i> / rows_pair_gacc (build_pair_kernel.h,
+  one cooperative scenario per row): the P chain once, two free-response
+  chains on shared multipliers, and the 8-accumulator Gram of the canonical
+  columns, split into blocks of at most 30 asm operands.
+
 Every block opens with `s_nop 1`: a VALU write of a VGPR followed by a DPP read
 of it needs two wait states and hipcc does not pad inside an asm statement
 (cdna_hip_programming.md §5.7).  No DPP source is written inside a block.
@@ -178,6 +183,103 @@ def chain_gacc_tail(ns, ny, nd, nut, nu, mm, split):
             f"  asm({body}\n      : {outs}\n      : {ins});\n}}\n")
 
 
+# Shared-form kernel (build_pair_kernel.h): one scenario of two cooperative
+# QPs per row.  (NS, NY, ND, NUT, NU, M): one P chain, two free-response
+# chains (aS0 / aS1 share the multipliers mS), and the full Gram of the
+# M * NUT canonical columns: acc[a] += bcast_a(cv[o]) * cv[o], a < M * NUT.
+PAIRS = [(11, 3, 2, 4, 2, 2)]
+PAIR_SPLIT = 5   # link groups of the head block (CMPC_ROWS_SPLIT's default)
+PAIR_PARTS = 2   # blocks after the head: an asm statement takes at most 30 operands
+
+
+def pair_block(name, tmpl, ns, ny, nd, nut, mm, l0, l1, carriers, gslice):
+    """Link groups l0 .. l1-1 of the five chains (NY rows of P, the two free
+    responses), `carriers`: the delayed-input carriers of both free responses
+    after them, and the gather FMAs gslice = (first, last) of the step's
+    NY * M * NUT spread between the link groups.  Slot 1's delayed inputs are
+    slot 0's in swapped order, and its own kernel adds its first one first:
+    carrier 16 - 1 with mS[NS + ND - 1], down to carrier 16 - ND."""
+    ncol = mm * nut
+    ops_out, ops_in = [], []
+
+    def out(expr):
+        ops_out.append(expr)
+        return len(ops_out) - 1
+
+    aP = [out(f"aP[{o}]") for o in range(ny)]
+    aS = [out("aS0"), out("aS1")]
+    g0, g1 = gslice
+    acc = [out(f"acc[{a}]") for a in range(ncol)] if g1 > g0 else []
+    n_out = len(ops_out)
+
+    def inp(expr):
+        ops_in.append(expr)
+        return n_out + len(ops_in) - 1
+
+    pP = [inp(f"pP[{o}]") for o in range(ny)]
+    pS = [inp("pS0"), inp("pS1")]
+    mP = {l: inp(f"mP[{l}]") for l in range(l0, l1)}
+    mS = {l: inp(f"mS[{l}]") for l in range(l0, l1)}
+    if carriers:
+        for k in range(nd):
+            mS[ns + k] = inp(f"mS[{ns + k}]")
+    cv = [inp(f"cv[{o}]") for o in range(ny)] if g1 > g0 else []
+    gl = []
+    for i in range(g0, g1):
+        o, a = divmod(i, ncol)
+        gl.append(f'"v_fmac_f64_dpp %{acc[a]}, %{cv[o]}, %{cv[o]} row_newbcast:{a} {CTRL}\\n\\t"')
+    nl = l1 - l0
+    per = -(-len(gl) // nl) if nl else 0
+    lines = ['"s_nop 1\\n\\t"']
+    for i, l in enumerate(range(l0, l1)):
+        for o in range(ny):
+            lines.append(f'"v_fmac_f64_dpp %{aP[o]}, %{pP[o]}, %{mP[l]} row_newbcast:{l} {CTRL}\\n\\t"')
+        for s in range(2):
+            lines.append(f'"v_fmac_f64_dpp %{aS[s]}, %{pS[s]}, %{mS[l]} row_newbcast:{l} {CTRL}\\n\\t"')
+        lines.extend(gl[i * per:(i + 1) * per])
+    if carriers:
+        for k in range(nd):
+            lines.append(f'"v_fmac_f64_dpp %{aS[0]}, %{pS[0]}, %{mS[ns + k]} row_newbcast:{16 - nd + k} {CTRL}\\n\\t"')
+            k1 = nd - 1 - k
+            lines.append(f'"v_fmac_f64_dpp %{aS[1]}, %{pS[1]}, %{mS[ns + k1]} row_newbcast:{16 - nd + k1} {CTRL}\\n\\t"')
+    assert len(ops_out) + len(ops_in) <= 30, (name, len(ops_out) + len(ops_in))
+    outs = ", ".join(f'"+v"({e})' for e in ops_out)
+    ins = ", ".join(f'"v"({e})' for e in ops_in)
+    body = "\n      ".join(lines)
+    return (f"template <> __device__ __forceinline__ void {name}<{tmpl}>("
+            f"const double* pP, double pS0, double pS1, const double* mP, const double* mS, double* aP, "
+            f"double& aS0, double& aS1, const double* cv, double* acc) {{\n"
+            f"  asm({body}\n      : {outs}\n      : {ins});\n}}\n")
+
+
+def pair_gacc(ny, nut, mm):
+    ncol = mm * nut
+    lines = ['"s_nop 1\\n\\t"']
+    for o in range(ny):
+        for a in range(ncol):
+            lines.append(f'"v_fmac_f64_dpp %{a}, %{ncol + o}, %{ncol + o} row_newbcast:{a} {CTRL}\\n\\t"')
+    outs = ", ".join(f'"+v"(acc[{a}])' for a in range(ncol))
+    ins = ", ".join(f'"v"(cv[{o}])' for o in range(ny))
+    body = "\n      ".join(lines)
+    return (f"template <> __device__ __forceinline__ void rows_pair_gacc<{ny}, {nut}, {mm}>("
+            f"const double* cv, double* acc) {{\n"
+            f"  asm({body}\n      : {outs}\n      : {ins});\n}}\n")
+
+
+def pair_blocks(ns, ny, nd, nut, nu, mm):
+    tm = f"{ns}, {ny}, {nd}, {nut}, {mm}"
+    parts = [pair_block("rows_pair_head", tm, ns, ny, nd, nut, mm, 0, PAIR_SPLIT, False, (0, 0))]
+    nl = ns - PAIR_SPLIT
+    ng = ny * mm * nut
+    for i in range(PAIR_PARTS):
+        l0 = PAIR_SPLIT + nl * i // PAIR_PARTS
+        l1 = PAIR_SPLIT + nl * (i + 1) // PAIR_PARTS
+        gs = (ng * i // PAIR_PARTS, ng * (i + 1) // PAIR_PARTS)
+        parts.append(pair_block(f"rows_pair_part{i}", tm, ns, ny, nd, nut, mm, l0, l1, i == PAIR_PARTS - 1, gs))
+    parts.append(pair_gacc(ny, nut, mm))
+    return parts
+
+
 def main():
     parts = ["// Generated by gen_rows.py — do not edit.\n",
              "template <int NS, int NY, int ND> __device__ __forceinline__ void rows_chain("
@@ -204,6 +306,14 @@ def main():
             parts.append(chain_head(*h, sp))
         for c in FUSED:
             parts.append(chain_gacc_tail(*c, sp))
+    for name in ["rows_pair_head"] + [f"rows_pair_part{i}" for i in range(PAIR_PARTS)]:
+        parts.append("template <int NS, int NY, int ND, int NUT, int M> __device__ __forceinline__ void "
+                     f"{name}(const double*, double, double, const double*, const double*, double*, double&, "
+                     "double&, const double*, double*);\n")
+    parts.append("template <int NY, int NUT, int M> __device__ __forceinline__ void rows_pair_gacc("
+                 "const double*, double*);\n")
+    for c in PAIRS:
+        parts.extend(pair_blocks(*c))
     with open(OUT, "w") as fh:
         fh.write("\n".join(parts))
     print("wrote", OUT)

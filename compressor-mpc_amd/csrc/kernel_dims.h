@@ -64,6 +64,10 @@
 #define CMPC_FOR_CONTROL_CENT(F) CMPC_BUILD_DIMS(CMPC_COL_CTC, F)
 #define CMPC_FOR_CONTROL_DIST(F) CMPC_BUILD_DIMS(CMPC_COL_CTD, F)
 
+// the shared form of the row build (build_pair_kernel.h: one cooperative
+// scenario, S = 2, per row): F(ns, ny, nu, m)
+#define CMPC_FOR_BUILD_PAIR(F) F(11, 3, 2, 2) /* parallel coop */
+
 // Solve side: F(nV, nu, nVo) of the lane and the row iterate kernels
 #define CMPC_FOR_SOLVE(F)                          \
   F(4, 2, 4) /* coop / ncoop, S = 2, m = 2 */      \

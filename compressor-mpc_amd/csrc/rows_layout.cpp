@@ -411,6 +411,35 @@ void cmpc_rows_layout(const cmpc_dims& d, int nd, int nobs, int rec_len, RowsLay
   *out = best;
 }
 
+// The shared form's wave region on top of layout R (PairLayout,
+// cmpc_internal.h).  The hand-off areas keep R's offsets, so their accesses
+// keep R's modelled bank conflicts; slot 1's z entries and the second set of w
+// tables follow them, the w tables at R's residue mod 32.  ok: two four-wave
+// workgroups per CU fit (the kernel is compiled for two waves per SIMD) and
+// the group's staging fits the kernel's chunk counts.
+void cmpc_pair_layout(const cmpc_dims& d, const RowsLayout& R, int nd, int rec_len, int off_x, PairLayout* out) {
+  std::memset(out, 0, sizeof *out);
+  if (!R.ok || rec_len % 2) return;
+  const int zlen = 4 * R.U * d.ny;
+  out->z1_off = up(R.w_off, 2);
+  out->tail0 = off_x & ~1;
+  const int stage = 4 * (2 * rec_len - out->tail0);
+  int w = std::max(out->z1_off + zlen, stage);  // behind the staged records
+  while ((w - R.w_off) % 32) ++w;
+  out->w_off = w;
+  // w lines of D + 3 entries (make_layout), without the row layout's padding
+  int dmax = 0;
+  for (int c = 0; c < d.nu_tot; ++c) dmax = std::max(dmax, d.delay[c]);
+  out->WL = up(std::min(d.p + 2 + R.U, dmax + 3), 2);
+  out->per_wave = up(out->w_off + 4 * 2 * nd * out->WL, 2);
+  const size_t req = sizeof(double) * ((size_t)R.lds_block + (size_t)out->per_wave * CMPC_BUILD_WAVES);
+  const size_t lds = (req + 511) / 512 * 512 + 512;  // waves_with's allocation model
+  // the kernel stages a record in three 1 KiB blocks and its tail in one, and
+  // compares the record's head in CMPC_PAIR_CMP blocks of 64 entries
+  out->ok = 2 * lds <= (size_t)kLdsBytes && rec_len <= 384 && rec_len - out->tail0 <= 128 &&
+            off_x <= 64 * CMPC_PAIR_CMP && rec_len >= 64 * CMPC_PAIR_CMP && out->WL <= 64;
+}
+
 double cmpc_rows_layout_conflicts(const cmpc_dims& d, int nd, const RowsLayout& R, int wave) {
   return loop_conflicts(d, nd, R, wave);
 }

@@ -274,6 +274,42 @@ int cmpc_set_build_variant(cmpc_ctx* ctx, int variant);
  * launched (CMPC_BUILD_WAVE, CMPC_BUILD_ROWS or CMPC_BUILD_SPLIT), 0 before the
  * first build, <0 on a null context. */
 int cmpc_last_build_kernel(cmpc_ctx* ctx);
+/* Build pairing: a mode of the row build (CMPC_BUILD_ROWS, chosen or forced as
+ * above; cmpc_plan and cmpc_last_build_kernel report ROWS either way).  The
+ * two sub-controllers of a cooperative scenario linearise the same plant at
+ * the same point: their records' A, C and f are equal and slot 1's B is slot
+ * 0's with the columns rotated by nu.  The shared form builds one scenario per
+ * 16-lane row and computes the Markov chain once for both QPs; the QP buffer
+ * is bit-identical to the unpaired row build's.  Per scenario the kernel
+ * compares the two records' A, B, C and f as 64-bit integers; a group of four
+ * scenarios with any difference is built the long way (same results, about
+ * the unpaired cost), so records need not satisfy the assumption.
+ *   CMPC_PAIRING_AUTO  (default) the shared form where the configuration is
+ *                      eligible and the batch is large enough to gain
+ *   CMPC_PAIRING_OFF   never
+ *   CMPC_PAIRING_ON    whenever the row build runs a cmpc_build; an error
+ *                      naming the failed condition where the configuration is
+ *                      not eligible: from cmpc_set_build_pairing for the
+ *                      dimensions, from cmpc_build / cmpc_step for the weights
+ * Eligible: S = 2, nu_tot = 2 nu, delay[c] == delay[(c + nu) % nu_tot], the
+ * sub-controllers' L_W' (ywt's Cholesky factor) bitwise equal, a shared-form
+ * instance for (ns, ny, nu, m) (the parallel plant's cooperative set), plain
+ * hand-off lines (no ring) and LDS for two workgroups per CU.  The fused steps
+ * and the one-launch control step keep the unpaired kernels. */
+#define CMPC_PAIRING_AUTO 0
+#define CMPC_PAIRING_OFF 1
+#define CMPC_PAIRING_ON 2
+int cmpc_set_build_pairing(cmpc_ctx* ctx, int mode);
+/* The eligibility above, without a device (the batch size aside): 1 or 0.
+ * lwt_s0 / lwt_s1: the two sub-controllers' L_W' tables (ny x ny, row-major),
+ * or null to leave the weights out.  cmpc_build_pairing_reason: "" when
+ * eligible, else the failed condition. */
+int cmpc_build_pairing_available(const cmpc_dims* dims, const double* lwt_s0, const double* lwt_s1);
+const char* cmpc_build_pairing_reason(const cmpc_dims* dims, const double* lwt_s0, const double* lwt_s1);
+/* Scenarios the last cmpc_build (or unfused cmpc_step) built in the shared
+ * form; the rest of the batch was built the long way.  -1 if that build was
+ * not the shared form, < -1 on error.  Synchronises the context's stream. */
+int cmpc_last_build_shared_scenarios(cmpc_ctx* ctx);
 /* Solve (cmpc_iterate / cmpc_init_warmstart / cmpc_get_input; the same
  * results bit for bit):
  *   CMPC_SOLVE_LANE  one QP per lane
