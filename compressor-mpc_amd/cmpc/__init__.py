@@ -22,7 +22,8 @@ from ._abi import (CMPC_BUILD_AUTO, CMPC_BUILD_ROWS, CMPC_BUILD_SPLIT, CMPC_BUIL
                    CMPC_APPLY_MOVE, CMPC_KERNEL_BUILD, CMPC_KERNEL_ITERATE,
                    CMPC_KERNEL_PRODUCE, CMPC_KERNEL_OBSERVE_POST, CMPC_KERNEL_OBSERVE_PRIOR, CMPC_QP_INFEASIBLE,
                    CMPC_QP_MAX_NWSR, CMPC_QP_NOT_PD, CMPC_QP_NONFINITE, CMPC_QP_OK, CMPC_TRACE, CmpcDims,
-                   CmpcLayout, CmpcPlan, CMPC_PLAN_DU_OTHER, CMPC_PLAN_REF_PROFILE, bptr, check, dptr, iptr, load_library, uptr)
+                   CmpcLayout, CmpcPlan, CMPC_PLAN_DU_OTHER, CMPC_PLAN_REF_PROFILE, CMPC_PLAN_SCENARIO_WEIGHTS, bptr,
+                   check, dptr, iptr, load_library, uptr)
 from .configs import ControllerConfig, SetupFile, reference_config, reference_observer_gain, reference_setup
 from .problem import ControllerArrays, controller_arrays, plant_input_from_plans
 
@@ -33,7 +34,8 @@ __all__ = ["Context", "ControllerConfig", "SetupFile", "reference_config", "refe
            "layout_of", "plan", "predict_available", "reference_profile_available", "CMPC_PLAN_REF_PROFILE", "plan_error_string", "rows_lds_model", "qp_solve_batch", "CMPC_APPLY_MOVE", "CMPC_TRACE", "CMPC_QP_OK",
            "CMPC_QP_MAX_NWSR", "CMPC_QP_INFEASIBLE", "CMPC_QP_NOT_PD",
            "CMPC_QP_NONFINITE", "build_pairing_available", "build_pairing_reason", "CMPC_PAIRING_AUTO",
-           "CMPC_PAIRING_OFF", "CMPC_PAIRING_ON"]
+           "CMPC_PAIRING_OFF", "CMPC_PAIRING_ON", "scenario_weights_available", "weight_factor",
+           "CMPC_PLAN_SCENARIO_WEIGHTS"]
 
 
 def layout_of(dims: CmpcDims) -> CmpcLayout:
@@ -43,14 +45,36 @@ def layout_of(dims: CmpcDims) -> CmpcLayout:
 
 
 def plan(dims: CmpcDims, cus: int, build: int = CMPC_BUILD_AUTO, solve: int = CMPC_SOLVE_AUTO,
-         step: int = CMPC_STEP_AUTO, K: int = 1, flags: int = 0) -> CmpcPlan:
+         step: int = CMPC_STEP_AUTO, K: int = 1, flags: int = 0, scenario_weights: bool = False) -> CmpcPlan:
     """Which kernels a batch of dims.B scenarios gets on a device of `cus`
     compute units under the three variants, for calls with K iterations
     and `flags` (CMPC_TRACE, CMPC_PLAN_DU_OTHER, CMPC_PLAN_REF_PROFILE): cmpc_plan, the library's own
-    selection (csrc/dispatch.cpp), answered without a device."""
+    selection (csrc/dispatch.cpp), answered without a device.
+    scenario_weights: per-slot weights are in force (CMPC_PLAN_SCENARIO_WEIGHTS)."""
     out = CmpcPlan()
+    if scenario_weights:
+        flags = int(flags) | CMPC_PLAN_SCENARIO_WEIGHTS
     check(load_library().cmpc_plan(ctypes.byref(dims), int(cus), int(build), int(solve), int(step), int(K),
                                    int(flags), ctypes.byref(out)), "cmpc_plan")
+    return out
+
+
+def scenario_weights_available(dims: CmpcDims) -> bool:
+    """Whether Context.set/bind_scenario_weights has a build kernel instance
+    for dims whose LDS fits with the per-wave weight tables (host only)."""
+    return bool(load_library().cmpc_scenario_weights_available(ctypes.byref(dims)))
+
+
+def weight_factor(ywt) -> np.ndarray:
+    """L_W' (upper triangular, ny x ny) with ywt = L_W L_W': the library's own
+    factorisation of an output weight (cmpc_weight_factor), for callers that
+    pack the blocks of Context.bind_scenario_weights themselves.  Raises for a
+    weight that is not symmetric positive semi-definite."""
+    W = np.ascontiguousarray(ywt, dtype=np.float64)
+    if W.ndim != 2 or W.shape[0] != W.shape[1]:
+        raise ValueError(f"ywt must be square, got {W.shape}")
+    out = np.zeros_like(W)
+    check(load_library().cmpc_weight_factor(W.shape[0], dptr(W), dptr(out)), "cmpc_weight_factor")
     return out
 
 
@@ -372,6 +396,41 @@ class Context:
         check(self.lib.cmpc_get_scenario_reference_profile(self._h, dptr(out)),
               "cmpc_get_scenario_reference_profile")
         return out
+
+    # -- per-scenario weights (include/cmpc.h) -------------------------------
+    def set_scenario_weights(self, uwt=None, ywt=None):
+        """Per-slot weights in slot order: uwt (B*S, nu, nu) symmetric and ywt
+        (B*S, ny, ny) symmetric positive semi-definite host arrays.  Slot q is
+        built with its own pair in place of the sub-controller's shared one
+        from the next build on.  Both None clears."""
+        if uwt is None and ywt is None:
+            check(self.lib.cmpc_set_scenario_weights(self._h, None, None), "cmpc_set_scenario_weights")
+            return
+        if uwt is None or ywt is None:
+            raise ValueError("give both uwt and ywt, or neither")
+        u = np.ascontiguousarray(uwt, np.float64)
+        y = np.ascontiguousarray(ywt, np.float64)
+        nu, ny = self.cfg.nu, self.cfg.ny
+        if u.size != self.nqp * nu * nu:
+            raise ValueError(f"uwt must hold B*S*nu*nu = {self.nqp * nu * nu} values, got {u.shape}")
+        if y.size != self.nqp * ny * ny:
+            raise ValueError(f"ywt must hold B*S*ny*ny = {self.nqp * ny * ny} values, got {y.shape}")
+        check(self.lib.cmpc_set_scenario_weights(self._h, dptr(u), dptr(y)), "cmpc_set_scenario_weights")
+
+    def bind_scenario_weights(self, device_ptr: int = 0):
+        """Bind a device-resident (B*S, ny*ny + nu*nu) f64 array of per-slot
+        blocks [L_W' | uwt], already factored (weight_factor); 0 clears."""
+        check(self.lib.cmpc_bind_scenario_weights(self._h, ctypes.c_void_p(device_ptr or None)),
+              "cmpc_bind_scenario_weights")
+
+    def get_scenario_weights(self):
+        """(uwt (B*S, nu, nu), L_W' (B*S, ny, ny)): the per-slot weights in
+        force (set or bound), the output weight as its factor; raises if none."""
+        nu, ny = self.cfg.nu, self.cfg.ny
+        u = np.zeros((self.nqp, nu, nu))
+        lw = np.zeros((self.nqp, ny, ny))
+        check(self.lib.cmpc_get_scenario_weights(self._h, dptr(u), dptr(lw)), "cmpc_get_scenario_weights")
+        return u, lw
 
     def set_scenario_constraints(self, lower=None, upper=None, rate_lower=None, rate_upper=None):
         """Per-slot input limits, four (B*S, nu) host arrays in slot order

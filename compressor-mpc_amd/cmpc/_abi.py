@@ -56,6 +56,11 @@ CMPC_PLAN_NO_BUILD = 2
 CMPC_PLAN_NO_ROWS_SOLVE = 3
 CMPC_PLAN_NO_SOLVE = 4
 CMPC_PLAN_NO_FUSED_STEP = 5
+CMPC_PLAN_PROFILE_NEEDS_SPLIT = 6
+CMPC_PLAN_SCENARIO_WEIGHTS = 0x400
+CMPC_PLAN_WEIGHTS_NEED_WAVE = 7
+CMPC_PLAN_WEIGHTS_NEED_SPLIT = 8
+CMPC_PLAN_NO_WEIGHTS_BUILD = 9
 
 
 class CmpcDims(ctypes.Structure):
@@ -143,6 +148,8 @@ EXPORTS = (
     "cmpc_get_scenario_reference_profile", "cmpc_reference_profile_available",
     "cmpc_set_build_pairing", "cmpc_build_pairing_available", "cmpc_build_pairing_reason",
     "cmpc_last_build_shared_scenarios",
+    "cmpc_set_scenario_weights", "cmpc_bind_scenario_weights", "cmpc_get_scenario_weights",
+    "cmpc_scenario_weights_available", "cmpc_weight_factor",
 )
 
 _lib = None
@@ -282,6 +289,11 @@ def load_library(path: str = LIB_PATH):
         "cmpc_build_pairing_available": ([P(CmpcDims), P(dbl), P(dbl)], ctypes.c_int),
         "cmpc_build_pairing_reason": ([P(CmpcDims), P(dbl), P(dbl)], ctypes.c_char_p),
         "cmpc_last_build_shared_scenarios": ([c_void], ctypes.c_int),
+        "cmpc_set_scenario_weights": ([c_void, P(dbl), P(dbl)], ctypes.c_int),
+        "cmpc_bind_scenario_weights": ([c_void, c_void], ctypes.c_int),
+        "cmpc_get_scenario_weights": ([c_void, P(dbl), P(dbl)], ctypes.c_int),
+        "cmpc_scenario_weights_available": ([P(CmpcDims)], ctypes.c_int),
+        "cmpc_weight_factor": ([ctypes.c_int, P(dbl), P(dbl)], ctypes.c_int),
         "cmpc_qp_solve_batch": ([ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(dbl),
                                  P(dbl), P(dbl), P(dbl), P(dbl), P(dbl), P(u32), ctypes.c_int,
                                  P(dbl), P(i32), P(i32), P(u32), P(ctypes.c_uint8), P(i32)],

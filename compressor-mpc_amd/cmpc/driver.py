@@ -141,6 +141,25 @@ class ClosedLoop:
             raise ValueError(f"y_offset must be (B = {self.B}, n_outputs), got {y_offset.shape}")
         self.ctx.set_scenario_reference(scenario_reference_offsets(self.cfg, y_offset))
 
+    def set_weights_per_scenario(self, uwt, ywt):
+        """Per-scenario weights for a tuning sweep: uwt (B, S, nu, nu) and ywt
+        (B, S, ny, ny), scenario b's sub-controller s taking uwt[b][s] and
+        ywt[b][s] in place of the shared arrays' from the next build on (call
+        before initialize for the whole run); both None restores the shared
+        weights.  Forwarded to Context.set_scenario_weights.  The loop's step
+        is the three calls observe_step / build + iterate / observe_apply, the
+        form a control step takes with per-slot weights in force."""
+        if uwt is None and ywt is None:
+            self.ctx.set_scenario_weights(None, None)
+            return
+        S, nu, ny = self.cfg.S, self.cfg.nu, self.cfg.ny
+        u = np.asarray(uwt, dtype=np.float64)
+        y = np.asarray(ywt, dtype=np.float64)
+        if u.shape != (self.B, S, nu, nu) or y.shape != (self.B, S, ny, ny):
+            raise ValueError(f"uwt must be (B = {self.B}, S = {S}, nu, nu) and ywt (B, S, ny, ny), "
+                             f"got {u.shape} and {y.shape}")
+        self.ctx.set_scenario_weights(u.reshape(self.B * S, nu, nu), y.reshape(self.B * S, ny, ny))
+
     def set_setpoint_schedule(self, schedule):
         """Per-scenario setpoint schedules with preview: (B, T, n_outputs)
         plant-output deviations per control step, in force from the next build

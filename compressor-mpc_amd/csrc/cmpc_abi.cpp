@@ -152,6 +152,14 @@ struct cmpc_ctx {
   // in the same way (cmpc_set/bind_scenario_reference_profile)
   const double* sc_dref = nullptr;
   double* own_sc_dref = nullptr;
+  // per-slot weights (nqp * (ny*ny + nu*nu), per slot [L_W' | uwt]) in force,
+  // or null; set or bound in the same way (cmpc_set/bind_scenario_weights).
+  // d_yref: the raw references [S][p][ny] their build and predict kernels read
+  // (cfg holds L_W' y_ref of the shared weights only), uploaded when stale
+  const double* sc_w = nullptr;
+  double* own_sc_w = nullptr;
+  double* d_yref = nullptr;
+  bool yref_dirty = true;
   int32_t *status = nullptr, *nwsr = nullptr, *ntrace = nullptr;
   char* out_block = nullptr;  // du | status | nwsr in one allocation: one D2H for cmpc_download
   bool out_host = false;      // out_block is page-locked host memory the kernels write in place
@@ -197,7 +205,7 @@ struct cmpc_ctx {
   bool bp_ok = false;
   BuildParams bp{};                     // cmpc_dispatch_params; bp_error: its error text
   const char* bp_error = nullptr;
-  cmpc_plan_t plans[16];
+  cmpc_plan_t plans[32];
   unsigned plans_valid = 0;             // bit k: plans[k] holds; cleared by cmpc_set_*_variant
   int last_step_fused = 0;
   // prediction (cmpc_predict): buffers allocated by the first call; pred_stale
@@ -229,35 +237,16 @@ int rebuild_cfg(cmpc_ctx* c) {
   c->h_cfg.assign((size_t)S * c->co.len, 0.0);
   for (int s = 0; s < S; ++s) {
     double* b = c->h_cfg.data() + (size_t)s * c->co.len;
-    // ywt = L_W L_W' (Cholesky; zero pivots allowed for PSD weights)
-    const double* W = c->ywt.data() + (size_t)s * ny * ny;
-    std::vector<double> Lw(ny * ny, 0.0);
-    double scale = 0;
-    for (int i = 0; i < ny * ny; ++i) scale = std::max(scale, std::fabs(W[i]));
-    for (int i = 0; i < ny; ++i)
-      for (int j = 0; j < ny; ++j)
-        if (std::fabs(W[i * ny + j] - W[j * ny + i]) > 1e-12 * (1 + scale))
-          return fail("ywt must be symmetric");
-    for (int j = 0; j < ny; ++j) {
-      double dd = W[j * ny + j];
-      for (int k = 0; k < j; ++k) dd -= Lw[j * ny + k] * Lw[j * ny + k];
-      if (dd < -1e-12 * (1 + scale)) return fail("ywt must be positive semi-definite");
-      if (dd <= 1e-14 * (1 + scale)) continue;  // zero column
-      const double ljj = std::sqrt(dd);
-      Lw[j * ny + j] = ljj;
-      for (int i = j + 1; i < ny; ++i) {
-        double v = W[i * ny + j];
-        for (int k = 0; k < j; ++k) v -= Lw[i * ny + k] * Lw[j * ny + k];
-        Lw[i * ny + j] = v / ljj;
-      }
-    }
-    for (int o = 0; o < ny; ++o)  // lwt = L_W' (upper triangular)
-      for (int o2 = 0; o2 < ny; ++o2) b[c->co.lwt + o * ny + o2] = Lw[o2 * ny + o];
+    // lwt = L_W' (upper triangular) with ywt = L_W L_W' (cmpc_weight_factor)
+    double* lwt = b + c->co.lwt;
+    if (const char* e = cmpc_weight_factor_error(ny, c->ywt.data() + (size_t)s * ny * ny, lwt)) return fail(e);
+    // yhat = L_W' y_ref (the build kernel's per-slot-weights instances repeat
+    // this order: from 0, ascending o2, a product then a sum)
     const double* yr = c->yref.data() + (size_t)s * p * ny;
     for (int r = 0; r < p; ++r)
       for (int o = 0; o < ny; ++o) {
         double v = 0;
-        for (int o2 = o; o2 < ny; ++o2) v += Lw[o2 * ny + o] * yr[r * ny + o2];
+        for (int o2 = o; o2 < ny; ++o2) v += lwt[o * ny + o2] * yr[r * ny + o2];
         b[c->co.yhat + r * ny + o] = v;
       }
     std::memcpy(b + c->co.uwt, c->uwt.data() + (size_t)s * nu * nu, sizeof(double) * nu * nu);
@@ -275,6 +264,18 @@ int rebuild_cfg(cmpc_ctx* c) {
 }
 
 int ensure_cfg(cmpc_ctx* c) { return c->cfg_dirty ? rebuild_cfg(c) : 0; }
+
+// per-slot weights in force: the raw references [S][p][ny] beside the cfg block
+int ensure_yref(cmpc_ctx* c) {
+  if (c->d_yref && !c->yref_dirty) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->d_yref) HIP_TRY(hipMalloc(&c->d_yref, sizeof(double) * c->yref.size()));
+  HIP_TRY(hipMemcpyAsync(c->d_yref, c->yref.data(), sizeof(double) * c->yref.size(), hipMemcpyHostToDevice,
+                         c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->yref_dirty = false;
+  return 0;
+}
 
 hipError_t pooled_event(cmpc_ctx* c, hipEvent_t* e) {
   if (!c->event_pool.empty()) {
@@ -394,11 +395,13 @@ int build_params(cmpc_ctx* c, BuildParams& P) {
 // is available, and the build calls report that error first.)
 const cmpc_plan_t& plan_of(cmpc_ctx* c, int K, bool trace, bool du_other) {
   const bool profile = c->sc_dref != nullptr;  // a reference profile is in force: no fused path
-  const unsigned k = (K > 0 ? 1u : 0u) | (trace ? 2u : 0u) | (du_other ? 4u : 0u) | (profile ? 8u : 0u);
+  const bool weights = c->sc_w != nullptr;     // per-slot weights are in force: the wave build, no fused path
+  const unsigned k = (K > 0 ? 1u : 0u) | (trace ? 2u : 0u) | (du_other ? 4u : 0u) | (profile ? 8u : 0u) |
+                     (weights ? 16u : 0u);
   if (!((c->plans_valid >> k) & 1)) {
     ensure_bp(c);
     c->plans[k] = cmpc_dispatch_plan(c->d, c->L, c->bp, c->build_variant, c->solve_variant, c->step_variant,
-                                     K > 0 ? 1 : 0, trace, du_other, profile);
+                                     K > 0 ? 1 : 0, trace, du_other, profile, weights);
     c->plans_valid |= 1u << k;
   }
   return c->plans[k];
@@ -547,7 +550,8 @@ int cmpc_destroy(cmpc_ctx* c) {
                   c->out_host ? nullptr : c->out_block,
                   c->own_ws ? c->own_ws : c->ws,
                   c->trace, c->ntrace, c->obs, c->d_obsM,
-                  c->stage, c->own_sc_dy, c->own_sc_limits, c->own_sc_dref, c->pred_y, c->pred_cost,
+                  c->stage, c->own_sc_dy, c->own_sc_limits, c->own_sc_dref, c->own_sc_w, c->d_yref, c->pred_y,
+                  c->pred_cost,
                   c->pair_cnt};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -608,6 +612,7 @@ int cmpc_set_reference(cmpc_ctx* c, int s, const double* y_ref) {
   std::memcpy(c->yref.data() + s * n, y_ref, sizeof(double) * n);
   c->have_r[s] = 1;
   c->cfg_dirty = true;
+  c->yref_dirty = true;
   c->pred_stale = "the reference has changed since the build (cmpc_set_reference)";
   return 0;
 }
@@ -880,6 +885,93 @@ int cmpc_get_scenario_reference_profile(cmpc_ctx* c, double* dref) {
   HIP_TRY(hipMemcpyAsync(dref, c->sc_dref, sizeof(double) * (size_t)c->nqp * c->d.p * c->d.ny,
                          hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// Per-slot weights (include/cmpc.h): set, bind and get as the families above;
+// the build, the reference-profile correction and cmpc_predict read the
+// packed blocks [L_W' | uwt].
+static const char* const kStaleWeights =
+    "the per-scenario weights have changed since the build (cmpc_set/bind_scenario_weights)";
+
+static int scenario_weights_refused(cmpc_ctx* c, const char* who) {
+  ensure_bp(c);
+  if (c->bp_error || !cmpc_build_weights_available(c->d, c->bp))
+    return fail(std::string(who) + ": " + cmpc_plan_error_string(CMPC_PLAN_NO_WEIGHTS_BUILD));
+  return 0;
+}
+
+int cmpc_weight_factor(int ny, const double* ywt, double* lwt) {
+  if (const char* e = cmpc_weight_factor_error(ny, ywt, lwt)) return fail(std::string("cmpc_weight_factor: ") + e);
+  return 0;
+}
+
+int cmpc_set_scenario_weights(cmpc_ctx* c, const double* uwt, const double* ywt) {
+  if (!c) return fail("null context");
+  if (!uwt && !ywt) {
+    if (c->sc_w) c->pred_stale = kStaleWeights;
+    c->sc_w = nullptr;
+    return 0;
+  }
+  if (!uwt || !ywt) return fail("cmpc_set_scenario_weights: give both weight arrays or none");
+  if (scenario_weights_refused(c, "cmpc_set_scenario_weights")) return -1;
+  const int ny = c->d.ny, nu = c->d.nu, nw = ny * ny + nu * nu;
+  const size_t nqp = (size_t)c->nqp;
+  std::vector<double> h(nqp * nw);  // per slot [L_W' | uwt]
+  for (size_t q = 0; q < nqp; ++q) {
+    const std::string slot = "cmpc_set_scenario_weights: slot " + std::to_string(q) + ": ";
+    const double *W = ywt + q * ny * ny, *U = uwt + q * nu * nu;
+    double* b = h.data() + q * nw;
+    double scale = 0;
+    for (int i = 0; i < ny * ny; ++i)
+      if (!std::isfinite(W[i])) return fail(slot + "weights must be finite");
+    for (int i = 0; i < nu * nu; ++i) {
+      if (!std::isfinite(U[i])) return fail(slot + "weights must be finite");
+      scale = std::max(scale, std::fabs(U[i]));
+    }
+    if (const char* e = cmpc_weight_factor_error(ny, W, b)) return fail(slot + e);
+    for (int i = 0; i < nu; ++i)
+      for (int j = 0; j < nu; ++j)
+        if (std::fabs(U[i * nu + j] - U[j * nu + i]) > 1e-12 * (1 + scale)) return fail(slot + "uwt must be symmetric");
+    std::memcpy(b + ny * ny, U, sizeof(double) * nu * nu);
+  }
+  c->pred_stale = kStaleWeights;
+  if (scenario_upload(c, &c->own_sc_w, h.data(), h.size())) return -1;
+  c->sc_w = c->own_sc_w;
+  return 0;
+}
+
+int cmpc_bind_scenario_weights(cmpc_ctx* c, const double* weights_device) {
+  if (!c) return fail("null context");
+  if (weights_device) {
+    if (scenario_weights_refused(c, "cmpc_bind_scenario_weights")) return -1;
+    const size_t nw = (size_t)c->d.ny * c->d.ny + (size_t)c->d.nu * c->d.nu;
+    if (!device_ptr_ok(c, weights_device, sizeof(double) * (size_t)c->nqp * nw)) {
+      (void)hipGetLastError();  // a failed pointer query is not a later launch's error
+      return fail("cmpc_bind_scenario_weights: not a device allocation of nqp * (ny*ny + nu*nu) doubles on the "
+                  "context's device");
+    }
+    if (reinterpret_cast<uintptr_t>(weights_device) % 8)
+      return fail("cmpc_bind_scenario_weights: misaligned array");
+  }
+  if (c->sc_w || weights_device) c->pred_stale = kStaleWeights;
+  c->sc_w = weights_device;
+  return 0;
+}
+
+int cmpc_get_scenario_weights(cmpc_ctx* c, double* uwt, double* ywt_factor) {
+  if (!c) return fail("null context");
+  if (!c->sc_w) return fail("cmpc_get_scenario_weights: no per-slot weights are set");
+  HIP_TRY(hipSetDevice(c->device));
+  const int ny = c->d.ny, nu = c->d.nu, nw = ny * ny + nu * nu;
+  const size_t nqp = (size_t)c->nqp;
+  std::vector<double> h(nqp * nw);
+  HIP_TRY(hipMemcpyAsync(h.data(), c->sc_w, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (size_t q = 0; q < nqp; ++q) {
+    if (ywt_factor) std::memcpy(ywt_factor + q * ny * ny, h.data() + q * nw, sizeof(double) * ny * ny);
+    if (uwt) std::memcpy(uwt + q * nu * nu, h.data() + q * nw + ny * ny, sizeof(double) * nu * nu);
+  }
   return 0;
 }
 
@@ -1767,6 +1859,7 @@ static int build_uses_pairing(cmpc_ctx* c, const BuildParams& P, const cmpc_plan
 int cmpc_build(cmpc_ctx* c) {
   if (!c) return fail("null context");
   if (ensure_cfg(c)) return -1;
+  if (c->sc_w && ensure_yref(c)) return -1;
   HIP_TRY(hipSetDevice(c->device));
   BuildParams P;
   if (build_params(c, P)) return -1;
@@ -1786,8 +1879,15 @@ int cmpc_build(cmpc_ctx* c) {
   TimedLaunch tl(c, CMPC_KERNEL_BUILD);
   if (tl.begin()) return -1;
   P.split = pl.build_kernel == CMPC_BUILD_SPLIT;
-  if (pl.build_kernel == CMPC_BUILD_ROWS ? cmpc_launch_build_rows(P, c->d, c->stream)
-                                         : cmpc_launch_build(P, c->d, c->stream))
+  if (c->sc_w) {  // per-slot weights: the one-QP-per-wave kernel's instances that load them
+    BuildParamsW W;
+    cmpc_dispatch_params_weights(c->d, P, &W);
+    W.sc_w = c->sc_w;
+    W.yref = c->d_yref;
+    if (pl.build_kernel != CMPC_BUILD_WAVE || cmpc_launch_build_weights(W, c->d, c->stream))
+      return plan_mismatch("build with per-scenario weights");
+  } else if (pl.build_kernel == CMPC_BUILD_ROWS ? cmpc_launch_build_rows(P, c->d, c->stream)
+                                                : cmpc_launch_build(P, c->d, c->stream))
     return plan_mismatch("build");
   if (check_launch("build kernel")) return -1;
   if (pair) ++c->pair_seq;
@@ -1800,6 +1900,7 @@ int cmpc_build(cmpc_ctx* c) {
     R.lin = P.lin;
     R.cfg = P.cfg;
     R.dref = c->sc_dref;
+    R.sc_w = c->sc_w;
     R.qp = P.qp;
     R.nqp = P.nqp;
     R.S = P.S;
@@ -2179,6 +2280,7 @@ int cmpc_predict(cmpc_ctx* c, const double* du, const double* du_other, uint32_t
   const size_t n = (size_t)c->nqp;
   if (!c->pred_y) HIP_TRY(hipMalloc(&c->pred_y, sizeof(double) * n * c->d.p * c->d.ny));
   if (!c->pred_cost) HIP_TRY(hipMalloc(&c->pred_cost, sizeof(double) * n * 2));
+  if (c->sc_w && ensure_yref(c)) return -1;
   PredictParams P;
   std::memset(&P, 0, sizeof P);
   P.lin = c->lin_bound ? c->lin_bound : c->lin;
@@ -2186,6 +2288,8 @@ int cmpc_predict(cmpc_ctx* c, const double* du, const double* du_other, uint32_t
   P.u_old = c->u_old;
   P.dy_ref = c->sc_dy;
   P.dref = c->sc_dref;
+  P.sc_w = c->sc_w;
+  P.yref = c->d_yref;  // (uploaded by the build that made the prediction current)
   P.du = du ? du : c->du;  // (page-locked host memory up to CMPC_HOST_OUT_MAX_QP slots: its device address)
   P.d = du_other;
   P.y_pred = c->pred_y;

@@ -211,6 +211,19 @@ struct BuildParams {
   SolveParams sv;
 };
 
+// Per-slot weights (cmpc_set/bind_scenario_weights): the
+// one-QP-per-wave build kernel's SCW instances take BuildParams and these.
+// lds_per_wave is then the grown region: the wave's private tables
+// [yhat_q yl_stride][L_W' ny*ny | uwt nu*nu] sit at tab_off, after the plain
+// region; lds_block is the zero slots alone (no block-shared tables).  Its own
+// struct, so that the kernel arguments of every other instance stay what they
+// are.
+struct BuildParamsW : BuildParams {
+  const double* sc_w;   // nqp * (ny*ny + nu*nu): per slot [L_W' | uwt]
+  const double* yref;   // S * p * ny raw references y_ref[s][r] (cfg holds L_W' y_ref only)
+  int tab_off;          // the private tables inside the wave region (doubles, even)
+};
+
 
 // Prediction (predict.hip, cmpc_predict): the predicted controlled outputs of
 // every QP slot over the horizon for given plans, and the two parts of the
@@ -221,6 +234,8 @@ struct PredictParams {
   const double* u_old;   // nqp * nu_tot
   const double* dy_ref;  // nqp * ny per-slot setpoint offsets, or null
   const double* dref;    // nqp * p * ny per-slot reference profiles (RefshiftParams), or null
+  const double* sc_w;    // nqp * (ny*ny + nu*nu) per-slot [L_W' | uwt] (BuildParamsW), or null: the cfg block's
+  const double* yref;    // S * p * ny raw references, read with sc_w (yhat[q] = L_W'[q] y_ref[s])
   const double* du;      // nqp * nV own plans
   const double* d;       // nqp * nVo other controllers' plans (the Jacobi iteration's order), or
                          // null: gathered from du of the scenario's other slots
@@ -237,12 +252,14 @@ struct PredictParams {
 int cmpc_launch_predict(const PredictParams& P, const cmpc_dims& d, void* stream);
 
 // Reference-profile correction (refshift.hip): f -= Su' w of
-// every QP slot, w[r] = ywt[s] dref[q][r], in place in the QP buffer right
-// after the build.  Reads the records the build read.
+// every QP slot, w[r] = ywt[s] dref[q][r] (ywt[q] with per-slot weights), in
+// place in the QP buffer right after the build.  Reads the records the build
+// read.
 struct RefshiftParams {
   const double* lin;     // nqp * rec_len
   const double* cfg;     // S * co.len
   const double* dref;    // nqp * p * ny, [slot][horizon row][output]
+  const double* sc_w;    // nqp * (ny*ny + nu*nu) per-slot [L_W' | uwt] (BuildParamsW), or null: the cfg block's
   double* qp;            // nqp * qp_len; only f (nV doubles at nV * nV) is read and written
   int nqp, S, p, rec_len, nobs, qp_len;
   int off_A, off_B, off_C;
@@ -362,6 +379,8 @@ struct CoupledParams {
 // availability predicate once more and returns -1 where it is false: the plan
 // and the launcher disagree, an internal error and never a fallback.
 int cmpc_launch_build(const BuildParams& P, const cmpc_dims& d, void* stream);  // P.split: the role-split kernel
+// the one-QP-per-wave kernel's per-slot-weights instances (BuildParamsW)
+int cmpc_launch_build_weights(const BuildParamsW& P, const cmpc_dims& d, void* stream);
 // Row-layout build kernel (build_rows.hip)
 int cmpc_launch_build_rows(const BuildParams& P, const cmpc_dims& d, void* stream);
 // Fused step (step_rows.hip): the row build kernel running the K Jacobi

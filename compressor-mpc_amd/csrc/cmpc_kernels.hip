@@ -27,6 +27,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "dispatch.h"
 #include "dpp_blocks.inc"
 #include "observer_body.h"
@@ -180,8 +182,22 @@
 // lane: bit-identical to SPLIT = false, with the two waves' instructions
 // sharing a SIMD's issue slots (one wave per SIMD issues an FP64 VALU about
 // every 8 cycles).
-template <int NS, int NY, int NUT, int NU, int M, int ND, int FUSE, bool SPLIT = false, int SW = 2>
-__device__ __forceinline__ void build_wave_body(const BuildParams& P) {
+//
+// SCW (per-slot weights, cmpc_set/bind_scenario_weights; FUSE = 0 and
+// SPLIT = false only): no block-shared tables; per QP the wave
+// loads the slot's [L_W' | uwt] block into its private tables
+// (BuildParamsW::tab_off) and fills yhat_q = L_W'[q] y_ref[s] there from the
+// raw references in global memory (the same rows for every QP of a wave, so
+// cache hits; a block-shared copy costs the LDS of a fourth workgroup per CU
+// at the bench shape), in the host's arithmetic order (rebuild_cfg,
+// cmpc_abi.cpp); yl, lwt and uwt point at the private copies and nothing else
+// changes, so a slot whose block equals sub-controller s's shared one gets the
+// bit-identical QP.
+template <int NS, int NY, int NUT, int NU, int M, int ND, int FUSE, bool SPLIT = false, int SW = 2,
+          bool SCW = false>
+__device__ __forceinline__ void build_wave_body(const std::conditional_t<SCW, BuildParamsW, BuildParams>& P) {
+  static_assert(!SCW || (FUSE == 0 && !SPLIT), "per-slot weights: the plain one-QP-per-wave build only");
+  constexpr int NSW = NY * NY + NU * NU;  // a slot's weight block: [L_W' | uwt]
   extern __shared__ __attribute__((aligned(16))) double smem[];
   constexpr int NV = NU * M;
   constexpr int NG = M * NUT + 1;  // gather lanes per row: QP columns (move k, input c), then z
@@ -227,7 +243,8 @@ __device__ __forceinline__ void build_wave_body(const BuildParams& P) {
   double* yl_all = smem;
   double* lw_all = yl_all + S * P.yl_stride;
   double* uw_all = lw_all + S * NY * NY;
-  double* zeros = uw_all + S * NU * NU;
+  // (SCW: no block-shared tables, the block region is the zeros alone)
+  double* zeros = SCW ? smem : uw_all + S * NU * NU;
   double* recl = smem + P.lds_block + (SPLIT ? 2 * wave : wave) * P.lds_per_wave;
   const int o_uold = rec_len, o_chat = o_uold + 8, o_kap = o_chat + NY * nobs;
   const int o_line = 0, o_w = P.w_off, o_zl = P.zs_off;
@@ -252,6 +269,13 @@ __device__ __forceinline__ void build_wave_body(const BuildParams& P) {
   double* lines = recl + o_line;
   double* zl = recl + o_zl;
   double* red = lines;
+  // SCW: the wave's private [yhat_q yl_stride][L_W' | uwt] after the plain region
+  double* wtab = recl;
+  if constexpr (SCW) {
+    static_assert(NSW <= 64, "one weight-block entry per lane");
+    wtab = recl + P.tab_off;
+  }
+  if constexpr (!SCW) {
   for (int e = threadIdx.x; e < S * P.yl_stride; e += 64 * WGW) {
     const int ss = e / P.yl_stride, t = e - ss * P.yl_stride;
     yl_all[e] = (t < pp * NY) ? P.cfg[(size_t)ss * P.co.len + P.co.yhat + t] : 0.0;
@@ -260,6 +284,7 @@ __device__ __forceinline__ void build_wave_body(const BuildParams& P) {
     lw_all[e] = P.cfg[(size_t)(e / (NY * NY)) * P.co.len + P.co.lwt + e % (NY * NY)];
   for (int e = threadIdx.x; e < S * NU * NU; e += 64 * WGW)
     uw_all[e] = P.cfg[(size_t)(e / (NU * NU)) * P.co.len + P.co.uwt + e % (NU * NU)];
+  }
   if (threadIdx.x < 16) zeros[threadIdx.x] = 0.0;
   __syncthreads();
 
@@ -342,6 +367,11 @@ __device__ __forceinline__ void build_wave_body(const BuildParams& P) {
                    : make_double2(0.0, 0.0);
   }
   double uold_l = (q < P.nqp && lane < NUT) ? P.u_old[(size_t)q * NUT + lane] : 0.0;
+  // SCW: the slot's [L_W' | uwt] block, one entry per lane, prefetched with the record
+  double scw_n = 0.0;
+  if constexpr (SCW) {
+    if (q < P.nqp && lane < NSW) scw_n = P.sc_w[(size_t)q * NSW + lane];
+  }
 
   // fair progress of a SIMD's waves: priority drops per completed quarter of
   // the wave's share (the SIMD otherwise favours its oldest wave and the
@@ -374,8 +404,8 @@ __device__ __forceinline__ void build_wave_body(const BuildParams& P) {
       ++done_qp;
     }
     const int s = q % S;
-    const double* yl = yl_all + s * P.yl_stride;
-    const double* lwt = lw_all + s * NY * NY;
+    const double* yl = SCW ? wtab : yl_all + s * P.yl_stride;
+    const double* lwt = SCW ? wtab + P.yl_stride : lw_all + s * NY * NY;
     // the slot's setpoint offset (BuildParams::dy_ref), requested here so that
     // the staging below covers its latency
     double dyr[NY];
@@ -392,6 +422,35 @@ __device__ __forceinline__ void build_wave_body(const BuildParams& P) {
       if (wA && ci < nchunk) reinterpret_cast<double2*>(recl)[ci] = chunk[i];
     }
     if (wA && lane < NUT) uol[lane] = uold_l;
+    if constexpr (SCW) {
+      // The wave's private tables, rewritten per QP with wl and chat below:
+      // after the previous QP's last reads (yhat_q in its horizon loop, uwt in
+      // its epilogue; the wave barrier that ends the QP loop body) and before
+      // this QP's first (L_W' for C_hat right below).  yhat_q[r][o] =
+      // sum_{o2 >= o} L_W'[o][o2] y_ref[s][r][o2] in the host's order
+      // (rebuild_cfg): from 0, ascending o2, a product then a sum (the tree
+      // builds with -ffp-contract=off), zero past row p - 1 as the shared table.
+      // Ahead of the next record's loads: a wait for the y_ref loads issued
+      // after them would drain that prefetch too.
+      if (lane < NSW) wtab[P.yl_stride + lane] = scw_n;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      const double* yraw = P.yref + (size_t)s * pp * NY;  // (global: the same rows for every QP of the wave)
+      for (int e = lane; e < P.yl_stride; e += 64) {
+        double v = 0.0;
+        if (e < pp * NY) {
+          const int r = e / NY, o = e - r * NY;
+#pragma unroll
+          for (int o2 = 0; o2 < NY; ++o2)
+            if (o2 >= o) v += lwt[o * NY + o2] * yraw[r * NY + o2];
+        }
+        wtab[e] = v;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
     {
       const int qn = SPLIT ? P.nqp : q + nwaves;
 #pragma unroll
@@ -402,6 +461,7 @@ __device__ __forceinline__ void build_wave_body(const BuildParams& P) {
                        : make_double2(0.0, 0.0);
       }
       uold_l = (qn < P.nqp && lane < NUT) ? P.u_old[(size_t)qn * NUT + lane] : 0.0;
+      if constexpr (SCW) scw_n = (qn < P.nqp && lane < NSW) ? P.sc_w[(size_t)qn * NSW + lane] : 0.0;
     }
     CMPC_WT(0)  // staging
     const double* Cs = recl + P.off_C;
@@ -732,7 +792,7 @@ __device__ __forceinline__ void build_wave_body(const BuildParams& P) {
       }
       double* out = P.qp + (size_t)q * P.qp_len;
       constexpr int nuo = NUT - NU, nVo = M * nuo;
-      const double* uwt = uw_all + s * NU * NU;
+      const double* uwt = SCW ? wtab + P.yl_stride + NY * NY : uw_all + s * NU * NU;
       const int k2 = col / NUT, c2 = col - k2 * NUT;
       if (col == M * NUT) {
 #pragma unroll
@@ -817,6 +877,15 @@ __global__ __launch_bounds__(64 * CMPC_BUILD_WAVES)
 __attribute__((amdgpu_waves_per_eu(FUSE ? 1 : 4, FUSE ? 1 : 4)))
 void cmpc_build_kernel(BuildParams P) {
   build_wave_body<NS, NY, NUT, NU, M, ND, FUSE>(P);
+}
+
+// per-slot weights (build_wave_body SCW): the launch shape of cmpc_build_kernel
+// with FUSE = 0.  A kernel of its own name, so that the instances above keep
+// their symbols and code.
+template <int NS, int NY, int NUT, int NU, int M, int ND>
+__global__ __launch_bounds__(64 * CMPC_BUILD_WAVES) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void cmpc_build_weights_kernel(BuildParamsW P) {
+  build_wave_body<NS, NY, NUT, NU, M, ND, 0, false, 2, true>(P);
 }
 
 // the role split (build_wave_body SPLIT): a two-wave workgroup per QP, two
@@ -1091,6 +1160,27 @@ int cmpc_launch_build(const BuildParams& P, const cmpc_dims& d, void* stream) {
   if (!cmpc_build_wave_available(d, P)) return -1;
   const size_t lds = sizeof(double) * ((size_t)P.lds_block + (size_t)P.lds_per_wave * CMPC_BUILD_WAVES);
   CMPC_FOR_BUILD_WAVE(BUILD_CASE)
+  return -1;
+}
+
+// per-slot weights: the persistent one-QP-per-wave launch of BUILD_CASE on the
+// SCW instances (the grown wave region is in P.lds_per_wave)
+#define BUILD_W_CASE(NS_, NY_, NU_, M_)                                                \
+  if (DIMS_ARE(NS_, NY_, NU_, M_)) {                                                   \
+    auto k_ = cmpc_build_weights_kernel<NS_, NY_, 4, NU_, M_, 2>;                      \
+    if (lds > 64 * 1024) cmpc_allow_lds(reinterpret_cast<const void*>(k_), lds);       \
+    int per_cu = cmpc_blocks_per_cu(k_, 64 * CMPC_BUILD_WAVES, lds);                   \
+    if (per_cu < 1) per_cu = std::max<int>(1, (int)((160 * 1024) / lds));             \
+    const int grid = std::max(1, std::min(P.grid, P.cus * per_cu));                   \
+    cmpc_launch(k_, dim3(grid), dim3(64 * CMPC_BUILD_WAVES), lds, s, P);               \
+    return 0;                                                                          \
+  }
+
+int cmpc_launch_build_weights(const BuildParamsW& P, const cmpc_dims& d, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!cmpc_build_weights_launchable(d, P) || !P.sc_w || !P.yref) return -1;
+  const size_t lds = sizeof(double) * ((size_t)P.lds_block + (size_t)P.lds_per_wave * CMPC_BUILD_WAVES);
+  CMPC_FOR_BUILD_WAVE(BUILD_W_CASE)
   return -1;
 }
 

@@ -6,6 +6,7 @@
 #include "dispatch.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 // ---------------------------------------------------------------------------
@@ -61,6 +62,39 @@ const char* cmpc_context_dims_error(const cmpc_dims& d, const cmpc_layout& L) {
   if (d.ny > 4) return "ny > 4 is not instantiated in the build kernel (one DPP row per output)";
   if (d.ns + d.ny + L.nd > 16) return "ns + ny + (delayed inputs) must be <= 16 (free-response DPP row)";
   if ((long long)d.B * d.S > (1LL << 30)) return "batch too large";
+  return nullptr;
+}
+
+// ---------------------------------------------------------------------------
+// the output weight's factor
+// ---------------------------------------------------------------------------
+// ywt = L_W L_W' (Cholesky; zero pivots allowed for PSD weights), stored as
+// lwt = L_W' (upper triangular, row-major).  The one place it is computed: the
+// shared weights (rebuild_cfg) and the per-slot ones (cmpc_set_scenario_weights)
+// go through it, so equal ywt give bitwise equal lwt.
+const char* cmpc_weight_factor_error(int ny, const double* W, double* lwt) {
+  if (ny < 1 || ny > 4 || !W || !lwt) return "weight factor: ny must be 1..4 and the arrays non-null";
+  double Lw[16] = {0};
+  double scale = 0;
+  for (int i = 0; i < ny * ny; ++i) scale = std::max(scale, std::fabs(W[i]));
+  for (int i = 0; i < ny; ++i)
+    for (int j = 0; j < ny; ++j)
+      if (std::fabs(W[i * ny + j] - W[j * ny + i]) > 1e-12 * (1 + scale)) return "ywt must be symmetric";
+  for (int j = 0; j < ny; ++j) {
+    double dd = W[j * ny + j];
+    for (int k = 0; k < j; ++k) dd -= Lw[j * ny + k] * Lw[j * ny + k];
+    if (dd < -1e-12 * (1 + scale)) return "ywt must be positive semi-definite";
+    if (dd <= 1e-14 * (1 + scale)) continue;  // zero column
+    const double ljj = std::sqrt(dd);
+    Lw[j * ny + j] = ljj;
+    for (int i = j + 1; i < ny; ++i) {
+      double v = W[i * ny + j];
+      for (int k = 0; k < j; ++k) v -= Lw[i * ny + k] * Lw[j * ny + k];
+      Lw[i * ny + j] = v / ljj;
+    }
+  }
+  for (int o = 0; o < ny; ++o)
+    for (int o2 = 0; o2 < ny; ++o2) lwt[o * ny + o2] = Lw[o2 * ny + o];
   return nullptr;
 }
 
@@ -233,6 +267,39 @@ bool wave_row_solver_fits(const cmpc_dims& d, const BuildParams& P) {
 }  // namespace
 
 bool cmpc_build_wave_available(const cmpc_dims& d, const BuildParams& P) { return in_build_wave(d, P); }
+
+// per-slot weights: the SCW instances have no block-shared tables (yhat, L_W'
+// and uwt are per wave), their block region is the zero slots alone
+constexpr int kWeightsLdsBlock = 32;
+static bool weights_lds_fits(int per_wave) {
+  return sizeof(double) * ((size_t)kWeightsLdsBlock + (size_t)per_wave * CMPC_BUILD_WAVES) <= kLdsLimitBytes;
+}
+
+bool cmpc_build_weights_available(const cmpc_dims& d, const BuildParams& P) {
+  return in_build_wave(d, P) && weights_lds_fits(P.lds_per_wave + cmpc_scenario_weights_region(d, P));
+}
+
+void cmpc_dispatch_params_weights(const cmpc_dims& d, const BuildParams& P, BuildParamsW* W) {
+  static_cast<BuildParams&>(*W) = P;
+  W->sc_w = nullptr;
+  W->yref = nullptr;
+  W->lds_block = kWeightsLdsBlock;
+  W->tab_off = P.lds_per_wave;  // (a multiple of 32)
+  W->lds_per_wave = P.lds_per_wave + cmpc_scenario_weights_region(d, P);
+}
+
+bool cmpc_build_weights_launchable(const cmpc_dims& d, const BuildParamsW& W) {
+  return in_build_wave(d, W) && !W.split && W.lds_block == kWeightsLdsBlock && W.tab_off > 0 && W.tab_off % 2 == 0 &&
+         W.lds_per_wave == W.tab_off + cmpc_scenario_weights_region(d, W) && weights_lds_fits(W.lds_per_wave);
+}
+
+extern "C" int cmpc_scenario_weights_available(const cmpc_dims* dims) {
+  cmpc_layout L;
+  if (!dims || cmpc_layout_error(dims, &L) || cmpc_context_dims_error(*dims, L)) return 0;
+  BuildParams P;
+  if (cmpc_dispatch_params(*dims, L, dims->B * dims->S, kCusFallback, &P)) return 0;
+  return cmpc_build_weights_available(*dims, P) ? 1 : 0;
+}
 
 int cmpc_build_rows_waves(const cmpc_dims& d, const BuildParams& P) {
   if (!rows_layout_usable(P.rows) || !in_build_rows(d, P)) return 0;
@@ -431,7 +498,7 @@ constexpr int kControlSplitQpPerCu = 1;
 
 cmpc_plan_t cmpc_dispatch_plan(const cmpc_dims& d, const cmpc_layout& L, const BuildParams& P, int build_variant,
                                int solve_variant, int step_variant, int K, bool trace, bool du_other,
-                               bool ref_profile) {
+                               bool ref_profile, bool scenario_weights) {
   const int nqp = P.nqp, cus = P.cus;
   cmpc_plan_t pl;
   std::memset(&pl, 0, sizeof pl);
@@ -439,7 +506,15 @@ cmpc_plan_t cmpc_dispatch_plan(const cmpc_dims& d, const cmpc_layout& L, const B
   // build
   const bool rows_fill = (nqp + 3) / 4 >= kRowsFillGroupsPerCu * cus;
   const bool want_rows_build = build_variant == CMPC_BUILD_ROWS || (build_variant == CMPC_BUILD_AUTO && rows_fill);
-  if (want_rows_build && cmpc_build_rows_available(d, P))
+  if (scenario_weights) {
+    // only the one-QP-per-wave kernel's SCW instances take per-slot weights
+    if (build_variant == CMPC_BUILD_ROWS || build_variant == CMPC_BUILD_SPLIT)
+      pl.build_error = CMPC_PLAN_WEIGHTS_NEED_WAVE;
+    else if (!cmpc_build_weights_available(d, P))
+      pl.build_error = CMPC_PLAN_NO_WEIGHTS_BUILD;
+    else
+      pl.build_kernel = CMPC_BUILD_WAVE;
+  } else if (want_rows_build && cmpc_build_rows_available(d, P))
     pl.build_kernel = CMPC_BUILD_ROWS;
   else if (build_variant == CMPC_BUILD_ROWS)
     pl.build_error = CMPC_PLAN_NO_ROWS_BUILD;
@@ -478,6 +553,9 @@ cmpc_plan_t cmpc_dispatch_plan(const cmpc_dims& d, const cmpc_layout& L, const B
   if (ref_profile) {
     // the correction of f runs between the build and the solve
     if (step_variant == CMPC_STEP_FUSED) pl.step_error = CMPC_PLAN_PROFILE_NEEDS_SPLIT;
+  } else if (scenario_weights) {
+    // no fused instance takes per-slot weights
+    if (step_variant == CMPC_STEP_FUSED) pl.step_error = CMPC_PLAN_WEIGHTS_NEED_SPLIT;
   } else if ((step_variant == CMPC_STEP_FUSED || auto_fuse) && K > 0 && own_plans) {
     const bool leave_rows_lane = rows_fill && L.nV <= kRowsLaneStepNvMax && step_variant == CMPC_STEP_AUTO;
     int kind = 0, solver = 0;
@@ -497,7 +575,7 @@ cmpc_plan_t cmpc_dispatch_plan(const cmpc_dims& d, const cmpc_layout& L, const B
   // control step: one launch (never traced), else the three calls
   pl.control_build_kernel = pl.step_build_kernel;
   pl.control_solve_kernel = pl.step_solve_kernel;
-  if (K > 0 && !ref_profile && step_variant != CMPC_STEP_SPLIT && build_variant == CMPC_BUILD_AUTO &&
+  if (K > 0 && !ref_profile && !scenario_weights && step_variant != CMPC_STEP_SPLIT && build_variant == CMPC_BUILD_AUTO &&
       solve_variant == CMPC_SOLVE_AUTO && nqp <= kControlQpPerCu * cus && own_plans) {
     const bool split = nqp <= kControlSplitQpPerCu * cus;
     const int grid = split ? std::max(1, (nqp + 1) / 2) : P.grid;
@@ -526,6 +604,15 @@ extern "C" const char* cmpc_plan_error_string(int e) {
     case CMPC_PLAN_PROFILE_NEEDS_SPLIT:
       return "cmpc_step: a reference profile is in force (cmpc_set/bind_scenario_reference_profile): its "
              "correction of f runs between the build and the solve, so CMPC_STEP_FUSED cannot be forced";
+    case CMPC_PLAN_WEIGHTS_NEED_WAVE:
+      return "per-scenario weights are in force (cmpc_set/bind_scenario_weights): only the one-QP-per-wave build "
+             "takes them, so CMPC_BUILD_ROWS and CMPC_BUILD_SPLIT cannot be forced";
+    case CMPC_PLAN_WEIGHTS_NEED_SPLIT:
+      return "cmpc_step: per-scenario weights are in force (cmpc_set/bind_scenario_weights): no fused kernel takes "
+             "them, so CMPC_STEP_FUSED cannot be forced";
+    case CMPC_PLAN_NO_WEIGHTS_BUILD:
+      return "per-scenario weights: no one-QP-per-wave build instance for these dimensions (ns, ny, nu, m), or its "
+             "LDS does not fit with the per-wave weight tables";
   }
   return "unknown plan error";
 }
@@ -543,6 +630,7 @@ const char* cmpc_plan_or_error(const cmpc_dims* dims, int cus, int build_variant
   BuildParams P;
   if (const char* e = cmpc_dispatch_params(*dims, L, dims->B * dims->S, cus, &P)) return e;
   *plan = cmpc_dispatch_plan(*dims, L, P, build_variant, solve_variant, step_variant, K, (flags & CMPC_TRACE) != 0,
-                             (flags & CMPC_PLAN_DU_OTHER) != 0, (flags & CMPC_PLAN_REF_PROFILE) != 0);
+                             (flags & CMPC_PLAN_DU_OTHER) != 0, (flags & CMPC_PLAN_REF_PROFILE) != 0,
+                             (flags & CMPC_PLAN_SCENARIO_WEIGHTS) != 0);
   return nullptr;
 }

@@ -16,6 +16,10 @@ constexpr int kProduceRowLds = 251;
 const char* cmpc_layout_error(const cmpc_dims* d, cmpc_layout* L);
 const char* cmpc_context_dims_error(const cmpc_dims& d, const cmpc_layout& L);
 
+// lwt = L_W' (upper triangular, ny x ny row-major) with ywt = L_W L_W': nullptr,
+// or why ywt is refused (not symmetric, not positive semi-definite)
+const char* cmpc_weight_factor_error(int ny, const double* ywt, double* lwt);
+
 inline int cmpc_qp_len(const cmpc_layout& L) { return (L.nV * L.nV + L.nV + L.nV * L.nVo + 1) / 2 * 2; }
 // LDS offset (doubles, 16-byte aligned) of the control step's producer rows
 inline int cmpc_control_pr_off(int S, int rec_len, int naug) { return ((S * rec_len + naug + 3) / 4) * 2; }
@@ -39,6 +43,21 @@ int cmpc_build_rows_waves(const cmpc_dims& d, const BuildParams& P);
 inline bool cmpc_build_rows_available(const cmpc_dims& d, const BuildParams& P) {
   return cmpc_build_rows_waves(d, P) != 0;
 }
+// Per-slot weights (cmpc_set/bind_scenario_weights, BuildParamsW): the SCW
+// instances of the one-QP-per-wave kernel keep a private yhat_q table
+// (yl_stride) and the slot's [L_W' | uwt] block per wave; the wave region grows
+// by this many doubles (even, so the 16-byte record chunks stay aligned)
+inline int cmpc_scenario_weights_region(const cmpc_dims& d, const BuildParams& P) {
+  return P.yl_stride + (d.ny * d.ny + d.nu * d.nu + 1) / 2 * 2;
+}
+// P: cmpc_dispatch_params.  An SCW instance exists (the WAVE column) and the
+// workgroup's LDS still fits with the grown wave regions.
+bool cmpc_build_weights_available(const cmpc_dims& d, const BuildParams& P);
+// cmpc_dispatch_params for the SCW instances: P with lds_per_wave grown and
+// tab_off set; the two pointers are left null
+void cmpc_dispatch_params_weights(const cmpc_dims& d, const BuildParams& P, BuildParamsW* W);
+// the launcher's check: W's wave region is the grown one and it fits
+bool cmpc_build_weights_launchable(const cmpc_dims& d, const BuildParamsW& W);
 // Shared form of the row build (cmpc_set_build_pairing): nullptr, or why the
 // configuration cannot use it.  lwt0 / lwt1: the two sub-controllers' L_W'
 // tables (ny x ny), compared bit for bit; null: not compared.
@@ -67,10 +86,14 @@ bool cmpc_refshift_instance(const cmpc_dims& d, const cmpc_layout& L);
 // and du_other describe the call (cmpc.h, cmpc_plan).  ref_profile: a
 // per-slot reference profile is in force (CMPC_PLAN_REF_PROFILE): the fused
 // paths keep f in registers and cannot take its correction, so the step is
-// two launches and the control step its three calls.
+// two launches and the control step its three calls.  scenario_weights:
+// per-slot weights are in force (CMPC_PLAN_SCENARIO_WEIGHTS): only the
+// one-QP-per-wave kernel's SCW instances take them, so the build is
+// CMPC_BUILD_WAVE at every batch size, ROWS or SPLIT forced is an error, and
+// nothing is fused (FUSED forced is an error).
 cmpc_plan_t cmpc_dispatch_plan(const cmpc_dims& d, const cmpc_layout& L, const BuildParams& P, int build_variant,
                                int solve_variant, int step_variant, int K, bool trace, bool du_other,
-                               bool ref_profile = false);
+                               bool ref_profile = false, bool scenario_weights = false);
 // cmpc_plan (cmpc.h) without the error slot: nullptr, or the error text
 const char* cmpc_plan_or_error(const cmpc_dims* dims, int cus, int build_variant, int solve_variant,
                                int step_variant, int K, uint32_t flags, cmpc_plan_t* plan);

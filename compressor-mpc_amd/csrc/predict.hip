@@ -18,7 +18,8 @@
 // step k0 + t, step t takes them by row_newbcast:t; the chunk's outputs go to
 // LDS, from where the row's lanes store them in 128-byte pieces and add up
 // J_track = 1/2 sum |L_W' (y - dy_ref - dref) - yhat|^2, one step per lane
-// (dref: the slot's reference profile where one is in force).
+// (dref: the slot's reference profile where one is in force; L_W', yhat and
+// uwt are the slot's own where per-slot weights are, PredictParams::sc_w).
 #include "cmpc_internal.h"
 #include "dispatch.h"
 #include "dpp_blocks.inc"
@@ -116,6 +117,17 @@ __global__ __launch_bounds__(64) void cmpc_predict_kernel(PredictParams P) {
 #pragma unroll
   for (int i = 0; i < NY * NY; ++i) lw[i] = cfg[P.co.lwt + i];
   const double* yhat = cfg + P.co.yhat;
+  const double* uw = cfg + P.co.uwt;
+  // per-slot weights: the slot's [L_W' | uwt] block, and
+  // yhat[q] = L_W'[q] y_ref[s] formed from the raw references below
+  const double* yraw = nullptr;
+  if (P.sc_w) {
+    const double* wq = P.sc_w + (size_t)q * (NY * NY + NU * NU);
+#pragma unroll
+    for (int i = 0; i < NY * NY; ++i) lw[i] = wq[i];
+    uw = wq + NY * NY;
+    yraw = P.yref + (size_t)s * P.p * NY;
+  }
   double* yout = P.y_pred + (size_t)q * P.p * NY;
 
   double x = 0.0, jt = 0.0;
@@ -162,7 +174,14 @@ __global__ __launch_bounds__(64) void cmpc_predict_kernel(PredictParams P) {
       }
 #pragma unroll
       for (int i = 0; i < NY; ++i) {
-        double r = -yhat[(size_t)k * NY + i];
+        double yh = 0.0;
+        if (yraw) {  // the build's order: from 0, ascending j, a product then a sum
+#pragma unroll
+          for (int j = i; j < NY; ++j) yh += lw[i * NY + j] * yraw[(size_t)k * NY + j];
+        } else {
+          yh = yhat[(size_t)k * NY + i];
+        }
+        double r = -yh;
 #pragma unroll
         for (int j = 0; j < NY; ++j) r = fma(lw[i * NY + j], e[j], r);
         jt = fma(r, r, jt);
@@ -189,7 +208,7 @@ __global__ __launch_bounds__(64) void cmpc_predict_kernel(PredictParams P) {
       for (int a = 0; a < NU; ++a) {
         double t = 0.0;
 #pragma unroll
-        for (int b = 0; b < NU; ++b) t = fma(cfg[P.co.uwt + a * NU + b], plan(b, mv), t);
+        for (int b = 0; b < NU; ++b) t = fma(uw[a * NU + b], plan(b, mv), t);
         jm = fma(plan(a, mv), t, jm);
       }
     P.cost[(size_t)q * 2] = 0.5 * jt;

@@ -1,7 +1,8 @@
 // Reference-profile correction (cmpc_set_scenario_reference_profile,
 // DESIGN.md §3.12): with slot q tracking y_ref[s][r] + dy_ref[q] + dref[q][r]
 // the QP of the build changes only in
-//   f <- f - g,   g = Su' w,   w[r] = ywt[s] dref[q][r]   (r = 0..p-1);
+//   f <- f - g,   g = Su' w,   w[r] = ywt[s] dref[q][r]   (r = 0..p-1;
+//   ywt[q] where per-slot weights are in force, RefshiftParams::sc_w);
 // H and G do not depend on the reference.  Su is never formed: Su' w is the
 // adjoint of the forward model predict.hip steps, one backward sweep
 //   lam <- A' lam + Cx' w[k],   k = p-1 .. 0,
@@ -105,6 +106,11 @@ __global__ __launch_bounds__(64) void cmpc_refshift_kernel(RefshiftParams P) {
   double lw[NY * NY];
 #pragma unroll
   for (int i = 0; i < NY * NY; ++i) lw[i] = cfg[P.co.lwt + i];
+  if (P.sc_w) {  // per-slot weights: w = L_W[q] (L_W'[q] dref)
+    const double* wq = P.sc_w + (size_t)q * (NY * NY + NU * NU);
+#pragma unroll
+    for (int i = 0; i < NY * NY; ++i) lw[i] = wq[i];
+  }
   const double* dq = P.dref + (size_t)q * P.p * NY;
 
   double g[M];

@@ -212,7 +212,8 @@ int cmpc_get_scenario_constraints(cmpc_ctx* ctx, double* lower, double* upper, d
  * controller sees coming inside its horizon (preview), are profiles.
  *
  * H and G do not depend on the reference and f is affine in it: the profile
- * changes the QP only by f <- f - Su' w, w[r] = ywt[s] dref[q][r].  cmpc_build
+ * changes the QP only by f <- f - Su' w, w[r] = ywt[s] dref[q][r] (ywt[q]
+ * where per-slot weights are in force, below).  cmpc_build
  * launches a correction kernel (refshift.hip) right after its build kernel,
  * on the same stream: a backward sweep over the slot's record that never
  * forms Su, and one FP64 subtraction per entry of f in place; H and G are
@@ -243,6 +244,60 @@ int cmpc_set_scenario_reference_profile(cmpc_ctx* ctx, const double* dref /* B*S
 int cmpc_bind_scenario_reference_profile(cmpc_ctx* ctx, const double* dref_device /* B*S*p*ny */);
 int cmpc_get_scenario_reference_profile(cmpc_ctx* ctx, double* dref);
 int cmpc_reference_profile_available(const cmpc_dims* dims);
+
+/* Per-scenario weights (slot order q = b*S + s).
+ *
+ * With per-slot weights in force slot q is built with its own ywt[q] (ny x ny,
+ * symmetric positive semi-definite) and uwt[q] (nu x nu, symmetric) in place
+ * of cmpc_set_weights(s): a sweep of the output and move weights over a grid
+ * or a random design, on the same plant and the same disturbances, is one
+ * batch.  The shared weights must still be set; they stay in force for
+ * anything per-slot weights do not cover, and come back after a clear.
+ *
+ * Weights change H and G, so unlike a reference profile they cannot be a
+ * correction after the build: the one-QP-per-wave build kernel has instances
+ * that load the slot's block [L_W'[q] | uwt[q]] (ywt[q] = L_W[q] L_W'[q]) into
+ * a per-wave table and form yhat[q] = L_W'[q] y_ref[s] there.  A slot whose
+ * block equals sub-controller s's shared one bit for bit gets the
+ * bit-identical H, f and G of CMPC_BUILD_WAVE.  Only that kernel takes them:
+ * the build is CMPC_BUILD_WAVE at every batch size under CMPC_BUILD_AUTO
+ * (cmpc_last_build_kernel reports it), CMPC_BUILD_ROWS or CMPC_BUILD_SPLIT
+ * forced fails (CMPC_PLAN_WEIGHTS_NEED_WAVE), and nothing is fused: cmpc_step
+ * runs as cmpc_build + cmpc_iterate (cmpc_last_step_fused() == 0),
+ * CMPC_STEP_FUSED forced fails (CMPC_PLAN_WEIGHTS_NEED_SPLIT) and
+ * cmpc_control_step* runs as its three calls.  cmpc_plan answers for this
+ * case under CMPC_PLAN_SCENARIO_WEIGHTS.  Build pairing applies to the row
+ * build only and needs nothing.  cmpc_predict and a reference profile's
+ * correction read the slot's block too (ywt[q], uwt[q] in their formulae).
+ * With nothing set (the default, and the state after a clear) every call
+ * computes exactly what it did without per-slot weights.
+ *
+ * cmpc_weight_factor (host only): lwt = L_W' (upper triangular, ny x ny
+ * row-major) with ywt = L_W L_W', the Cholesky factorisation the library uses
+ * for the shared weights as well, so a slot whose ywt equals the shared one
+ * bit for bit gets a bit-identical L_W'.  It tests symmetry and allows zero
+ * pivots for positive semi-definite weights; -1 with a message otherwise.
+ * cmpc_set_scenario_weights: host arrays, every slot validated (finite values,
+ * ywt symmetric positive semi-definite as above, uwt symmetric; the message
+ * names the first bad slot), factored on the host and copied on the ctx stream
+ * into a buffer allocated on first use, one block per slot
+ * [L_W' (ny*ny) | uwt (nu*nu)].  Both pointers NULL clears; exactly one NULL is
+ * an error.
+ * cmpc_bind_scenario_weights: the same packed per-slot blocks in device
+ * memory, already factored (cmpc_weight_factor), read in place by every later
+ * call; checked as cmpc_bind_state checks its pointers, for
+ * B*S*(ny*ny + nu*nu) doubles, 8-byte aligned; not validated.  NULL clears.
+ * cmpc_get_scenario_weights: host copies of what is in force, uwt and the
+ * factor L_W' (either pointer may be NULL); -1 if nothing is.
+ * set and bind take effect at the next build, and fail with a message where
+ * cmpc_scenario_weights_available is 0 (host only: 1 for every dimension set
+ * with a one-QP-per-wave build instance whose LDS still fits with the
+ * per-wave tables, 0 elsewhere). */
+int cmpc_set_scenario_weights(cmpc_ctx* ctx, const double* uwt /* B*S*nu*nu */, const double* ywt /* B*S*ny*ny */);
+int cmpc_bind_scenario_weights(cmpc_ctx* ctx, const double* weights_device /* B*S*(ny*ny + nu*nu) */);
+int cmpc_get_scenario_weights(cmpc_ctx* ctx, double* uwt, double* ywt_factor /* L_W', B*S*ny*ny */);
+int cmpc_scenario_weights_available(const cmpc_dims* dims);
+int cmpc_weight_factor(int ny, const double* ywt, double* lwt);
 
 /* Hot path. */
 int cmpc_build(cmpc_ctx* ctx);
@@ -349,10 +404,15 @@ int cmpc_last_step_fused(cmpc_ctx* ctx);
  * a cmpc_get_input with the other controllers' plans given;
  * CMPC_PLAN_REF_PROFILE: a reference profile is in force, so no path is
  * fused: step_fused, control_fused, control_grid and control_polled are 0 and
- * the step's kernels are those of CMPC_STEP_SPLIT).  A context takes the same
- * plan with its device's CU count. */
+ * the step's kernels are those of CMPC_STEP_SPLIT;
+ * CMPC_PLAN_SCENARIO_WEIGHTS: per-slot weights are in force, so the build is
+ * CMPC_BUILD_WAVE at every batch size under CMPC_BUILD_AUTO, ROWS or SPLIT
+ * forced is a build error, and no path is fused, as under
+ * CMPC_PLAN_REF_PROFILE).  A context takes the same plan with its device's CU
+ * count. */
 #define CMPC_PLAN_DU_OTHER 0x100u
 #define CMPC_PLAN_REF_PROFILE 0x200u
+#define CMPC_PLAN_SCENARIO_WEIGHTS 0x400u
 /* plan errors: what a call fails with (cmpc_plan_error_string) */
 #define CMPC_PLAN_OK 0
 #define CMPC_PLAN_NO_ROWS_BUILD 1  /* CMPC_BUILD_ROWS forced, not available */
@@ -361,6 +421,9 @@ int cmpc_last_step_fused(cmpc_ctx* ctx);
 #define CMPC_PLAN_NO_SOLVE 4       /* no solve kernel instance for (nV, nu, nVo) */
 #define CMPC_PLAN_NO_FUSED_STEP 5  /* CMPC_STEP_FUSED forced, not available */
 #define CMPC_PLAN_PROFILE_NEEDS_SPLIT 6  /* CMPC_STEP_FUSED forced with a reference profile in force */
+#define CMPC_PLAN_WEIGHTS_NEED_WAVE 7    /* CMPC_BUILD_ROWS or CMPC_BUILD_SPLIT forced with per-slot weights in force */
+#define CMPC_PLAN_WEIGHTS_NEED_SPLIT 8   /* CMPC_STEP_FUSED forced with per-slot weights in force */
+#define CMPC_PLAN_NO_WEIGHTS_BUILD 9     /* per-slot weights: no build instance, or its LDS does not fit */
 typedef struct cmpc_plan_t {
   /* cmpc_build */
   int32_t build_kernel;        /* CMPC_BUILD_WAVE / ROWS / SPLIT; 0 with build_error */
@@ -373,7 +436,8 @@ typedef struct cmpc_plan_t {
    * after it */
   int32_t step_fused;
   int32_t step_build_kernel, step_solve_kernel;
-  int32_t step_error;          /* CMPC_PLAN_NO_FUSED_STEP, CMPC_PLAN_PROFILE_NEEDS_SPLIT or 0 */
+  int32_t step_error;          /* CMPC_PLAN_NO_FUSED_STEP, CMPC_PLAN_PROFILE_NEEDS_SPLIT,
+                                  CMPC_PLAN_WEIGHTS_NEED_SPLIT or 0 */
   /* cmpc_control_step: one launch, or the three calls with cmpc_step as above */
   int32_t control_fused;
   int32_t control_build_kernel, control_solve_kernel;
@@ -418,7 +482,9 @@ int cmpc_download_trace(cmpc_ctx* ctx, uint8_t* trace, int32_t* ntrace);
  *   e[r]      = y_pred[r] - (y_ref[s][r] + dy_ref[q] + dref[q][r])
  *   J_track   = 1/2 sum_r e[r]' ywt[s] e[r]
  *   J_move    = 1/2 sum_mv du_mv' uwt[s] du_mv
- * with xa the record's dx_aug after AdjustAllDelayedStates (u_old).  Then
+ * with xa the record's dx_aug after AdjustAllDelayedStates (u_old); ywt[q] and
+ * uwt[q] in place of ywt[s] and uwt[s] where per-slot weights are in force
+ * (cmpc_set/bind_scenario_weights).  Then
  *   J_track + J_move - J_track(du = 0) = 1/2 du' H du + (f + G d)' du,
  * the objective of the QP the step solved.  Limits do not enter.
  *
@@ -442,7 +508,8 @@ int cmpc_download_trace(cmpc_ctx* ctx, uint8_t* trace, int32_t* ntrace);
  * cmpc_control_step*, cmpc_set_state with u_old, cmpc_bind_state,
  * cmpc_upload_lin, cmpc_bind_lin, cmpc_produce_lin, cmpc_observe_step*,
  * cmpc_observer_init*, cmpc_set_weights, cmpc_set_reference,
- * cmpc_set/bind_scenario_reference, cmpc_set/bind_scenario_reference_profile.
+ * cmpc_set/bind_scenario_reference, cmpc_set/bind_scenario_reference_profile,
+ * cmpc_set/bind_scenario_weights.
  * The flag lives on the host: writes the
  * library does not see (a producer writing through cmpc_lin_device(), bound
  * state or offsets changed by the caller's kernels) are the caller's to order.
