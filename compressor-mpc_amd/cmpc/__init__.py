@@ -432,6 +432,33 @@ class Context:
         check(self.lib.cmpc_get_scenario_weights(self._h, dptr(u), dptr(lw)), "cmpc_get_scenario_weights")
         return u, lw
 
+    # -- per-scenario boundary pressures of the model (include/cmpc.h) -------
+    def set_scenario_pressures(self, pressures=None):
+        """Per-scenario boundary pressures of the controller's model, a (B, 2)
+        host array of [p_in, p_out], finite and positive.  While in force the
+        producer (produce_lin, observer_init, observe_step, control_step)
+        linearises scenario b at its own pair and the scalar p_in / p_out
+        arguments are ignored.  None clears."""
+        if pressures is None:
+            check(self.lib.cmpc_set_scenario_pressures(self._h, None), "cmpc_set_scenario_pressures")
+            return
+        p = np.ascontiguousarray(pressures, np.float64)
+        if p.shape != (self.B, 2):
+            raise ValueError(f"pressures must be (B = {self.B}, 2), got {p.shape}")
+        check(self.lib.cmpc_set_scenario_pressures(self._h, dptr(p)), "cmpc_set_scenario_pressures")
+
+    def bind_scenario_pressures(self, device_ptr: int = 0):
+        """Bind a device-resident (B, 2) f64 array of [p_in, p_out], read at
+        each launch (the caller may rewrite it between steps); 0 clears."""
+        check(self.lib.cmpc_bind_scenario_pressures(self._h, ctypes.c_void_p(device_ptr or None)),
+              "cmpc_bind_scenario_pressures")
+
+    def get_scenario_pressures(self) -> np.ndarray:
+        """(B, 2): the pressures in force (set or bound); raises if none."""
+        out = np.zeros((self.B, 2))
+        check(self.lib.cmpc_get_scenario_pressures(self._h, dptr(out)), "cmpc_get_scenario_pressures")
+        return out
+
     def set_scenario_constraints(self, lower=None, upper=None, rate_lower=None, rate_upper=None):
         """Per-slot input limits, four (B*S, nu) host arrays in slot order
         (scenario_limits maps plant inputs to slots); all None clears."""

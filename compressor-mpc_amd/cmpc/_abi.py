@@ -150,6 +150,9 @@ EXPORTS = (
     "cmpc_last_build_shared_scenarios",
     "cmpc_set_scenario_weights", "cmpc_bind_scenario_weights", "cmpc_get_scenario_weights",
     "cmpc_scenario_weights_available", "cmpc_weight_factor",
+    "cmpc_set_scenario_pressures", "cmpc_bind_scenario_pressures", "cmpc_get_scenario_pressures",
+    "cmpc_sim_set_pressures", "cmpc_sim_set_pressures_host", "cmpc_sim_bind_pressures",
+    "cmpc_sim_get_pressures", "cmpc_check_pressures",
 )
 
 _lib = None
@@ -294,6 +297,14 @@ def load_library(path: str = LIB_PATH):
         "cmpc_get_scenario_weights": ([c_void, P(dbl), P(dbl)], ctypes.c_int),
         "cmpc_scenario_weights_available": ([P(CmpcDims)], ctypes.c_int),
         "cmpc_weight_factor": ([ctypes.c_int, P(dbl), P(dbl)], ctypes.c_int),
+        "cmpc_set_scenario_pressures": ([c_void, P(dbl)], ctypes.c_int),
+        "cmpc_bind_scenario_pressures": ([c_void, c_void], ctypes.c_int),
+        "cmpc_get_scenario_pressures": ([c_void, P(dbl)], ctypes.c_int),
+        "cmpc_sim_set_pressures": ([c_void, c_void], ctypes.c_int),
+        "cmpc_sim_set_pressures_host": ([c_void, P(dbl)], ctypes.c_int),
+        "cmpc_sim_bind_pressures": ([c_void, c_void], ctypes.c_int),
+        "cmpc_sim_get_pressures": ([c_void, P(dbl)], ctypes.c_int),
+        "cmpc_check_pressures": ([ctypes.c_int, P(dbl)], ctypes.c_int),
         "cmpc_qp_solve_batch": ([ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(dbl),
                                  P(dbl), P(dbl), P(dbl), P(dbl), P(dbl), P(u32), ctypes.c_int,
                                  P(dbl), P(i32), P(i32), P(u32), P(ctypes.c_uint8), P(i32)],

@@ -78,12 +78,19 @@ class ClosedLoop:
                    plant output, or None (set_setpoints changes them later)
     limits         (lower, upper, rate_lower, rate_upper), each (B, nu_tot) in
                    plant control order: per-scenario input limits, or None
-    Both are in force before initialize (the first build and the cold solves).
-    set_setpoint_schedule adds per-scenario setpoint schedules with preview.
+    pressures      (B, 2) per-scenario boundary pressures [p_in, p_out] of the
+                   plant, or None: the scalars p_in, p_out for every scenario
+    model_pressures  (B, 2) the same for the controller's model; None: the
+                   model follows `pressures`.  Passing both gives a
+                   plant/model mismatch study.
+    All are in force before initialize (the first build and the cold solves).
+    set_setpoint_schedule adds per-scenario setpoint schedules with preview,
+    set_pressures and set_pressure_schedule change the pressures during a run.
     """
 
     def __init__(self, cfg: ControllerConfig, arrays, M, x0, u_offset, K: int, device: int = 0,
-                 Ts: float = REF_TS, p_in: float = 1.0, p_out: float = 1.0, y_offset=None, limits=None):
+                 Ts: float = REF_TS, p_in: float = 1.0, p_out: float = 1.0, y_offset=None, limits=None,
+                 pressures=None, model_pressures=None):
         import torch
         self.torch = torch
         torch.cuda.init()
@@ -92,6 +99,9 @@ class ClosedLoop:
         self.p_in, self.p_out = p_in, p_out
         B = x0.shape[0]
         self.B, S = B, cfg.S
+        for a, what in ((pressures, "pressures"), (model_pressures, "model_pressures")):
+            if a is not None:   # (refused before anything is allocated)
+                self._pressure_check(a, what)
         self.sim = PlantSimulator(cfg.plant, B, device, p_in, p_out, REF_DELAYS, REF_CONTROL_INDEX)
         self.ctx = Context(cfg, B, device=device)
         self.ctx.set_stream(torch.cuda.current_stream(dev).cuda_stream)
@@ -113,6 +123,10 @@ class ClosedLoop:
         self._sched = []   # pending (t_start, plant-input offset (B, n_inputs) device)
         self._sp_sched = None   # setpoint schedule in slot order, (B, S, T, ny) device
         self._sp_window = None  # the bound reference profile, (B*S, p, ny) device
+        self._pp = self._pm = None            # bound pressures of plant and model, (B, 2) device
+        self._pp_sched = self._pm_sched = None  # their schedules, (B, T, 2) device
+        if pressures is not None or model_pressures is not None:
+            self.set_pressures(pressures, pressures if model_pressures is None else model_pressures)
 
     def set_segments(self, segments, u_default):
         """The setup file's `simulation` segments ([(offset change, end time)],
@@ -200,11 +214,83 @@ class ClosedLoop:
         idx = (self._sp_rows + (self.k + 1)).clamp_(max=T - 1)
         self._sp_window.copy_(self._sp_sched[:, :, idx, :].reshape(self._sp_window.shape))
 
+    def _pressure_array(self, a, what, sched=False):
+        a = self._pressure_check(a, what, sched)
+        return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+
+    def _pressure_check(self, a, what, sched=False):
+        a = np.asarray(a, dtype=np.float64)
+        if sched:
+            if a.ndim != 3 or a.shape[0] != self.B or a.shape[1] < 1 or a.shape[2] != 2:
+                raise ValueError(f"{what} must be (B = {self.B}, T >= 1, 2), got {a.shape}")
+        elif a.shape != (self.B, 2):
+            raise ValueError(f"{what} must be (B = {self.B}, 2), got {a.shape}")
+        if not np.isfinite(a).all() or not (a > 0).all():
+            raise ValueError(f"{what} must be finite and positive")
+        return a
+
+    def _bound_pressures(self, model: bool):
+        """The (B, 2) device array bound to the model or the plant, made and
+        bound at first use, starting from the scalars."""
+        cur = self._pm if model else self._pp
+        if cur is None:
+            cur = self.torch.tensor([self.p_in, self.p_out], dtype=self.torch.float64,
+                                    device=self.dev).repeat(self.B, 1).contiguous()
+            if model:
+                self._pm = cur
+                self.ctx.bind_scenario_pressures(cur.data_ptr())
+            else:
+                self._pp = cur
+                self.sim.bind_pressures(cur.data_ptr())
+        return cur
+
+    def set_pressures(self, plant=None, model=None):
+        """Per-scenario boundary pressures [p_in, p_out], each (B, 2): `plant`
+        for the plant's next integration, `model` for the controller's next
+        linearisation.  An argument left None keeps what is in force.  The
+        values go into device arrays bound to the simulator and the context
+        (PlantSimulator.bind_pressures, Context.bind_scenario_pressures), so a
+        call between two steps launches nothing but the copy.  A schedule
+        (set_pressure_schedule) overwrites them at its next step."""
+        new = [(m, self._pressure_array(a, w)) for m, a, w in ((False, plant, "plant"), (True, model, "model"))
+               if a is not None]
+        for m, a in new:
+            self._bound_pressures(m).copy_(a)
+
+    def set_pressure_schedule(self, plant, model=None):
+        """Per-scenario pressure schedules, each (B, T, 2) of [p_in, p_out] per
+        control step: at step k the controller linearises with
+        model[b][min(k, T - 1)] and the plant integrates [t_k, t_k + Ts] with
+        plant[b][min(k, T - 1)] (initialize linearises with row 0).  model
+        None leaves the model's pressures as they are: the plant's changes are
+        then an unmeasured disturbance.  The step's row is copied on the device
+        into the bound arrays (set_pressures).  plant None removes both
+        schedules; the arrays keep their last rows."""
+        if plant is None:
+            if model is not None:
+                raise ValueError("a model schedule needs a plant schedule")
+            self._pp_sched = self._pm_sched = None
+            return
+        pp = self._pressure_array(plant, "plant", sched=True)
+        pm = None if model is None else self._pressure_array(model, "model", sched=True)
+        self._pp_sched, self._pm_sched = pp, pm
+        self._bound_pressures(False)
+        if pm is not None:
+            self._bound_pressures(True)
+
+    def _pressure_rows(self):
+        """The schedules' rows of control step self.k into the bound arrays."""
+        for sch, model in ((self._pp_sched, False), (self._pm_sched, True)):
+            if sch is not None:
+                self._bound_pressures(model).copy_(sch[:, min(self.k, sch.shape[1] - 1), :])
+
     def initialize(self, dx_init=None):
         """SimulationSystem(x0, u_offset) + NerveCenter::Initialize(x0, 0,
         u_offset, y(x0), dx_init): the observers' state, the records at x0,
         the first build and the cold InitializeQPProblem solves."""
         self.sim.reset(self.x0, self.u_offset, self.Ts)
+        self.k = 0
+        self._pressure_rows()
         y0 = self.sim.output()
         dx = 0 if dx_init is None else self.torch.from_numpy(np.ascontiguousarray(dx_init)).to(self.dev)
         self.ctx.observer_init(self.x0.data_ptr(), self.u_offset.data_ptr(), y0.data_ptr(),
@@ -230,6 +316,7 @@ class ClosedLoop:
         # integrate_const's own time: start_time + step * dt of the current
         # Integrate call; its interval ends at time + dt
         t_int = self.t_seg + self.seg_step * self.Ts
+        self._pressure_rows()
         y = self.sim.output()
         # GetNextInputWithTiming(y): linearisation input GetPlantInput(u_old_,
         # u_offset_) with the controller's own offset (fixed at Initialize; the

@@ -79,6 +79,41 @@ class PlantSimulator:
         check(self.lib.cmpc_sim_set_offset(self._h, ctypes.c_void_p(u_offset.data_ptr())),
               "cmpc_sim_set_offset")
 
+    def set_pressures(self, pressures=None):
+        """Per-scenario boundary pressures of the plant, (B, 2) of [p_in,
+        p_out], read by every later integrate in place of the constructor's
+        scalars: a host array (checked finite and positive) or a device
+        tensor (copied, not checked).  None restores the scalars."""
+        if pressures is None:
+            check(self.lib.cmpc_sim_set_pressures(self._h, None), "cmpc_sim_set_pressures")
+            return
+        if isinstance(pressures, self.torch.Tensor):
+            if (tuple(pressures.shape) != (self.B, 2) or pressures.dtype != self.torch.float64
+                    or not pressures.is_cuda or not pressures.is_contiguous()):
+                raise ValueError(f"pressures must be a contiguous float64 device tensor (B = {self.B}, 2)")
+            check(self.lib.cmpc_sim_set_pressures(self._h, ctypes.c_void_p(pressures.data_ptr())),
+                  "cmpc_sim_set_pressures")
+            return
+        p = np.ascontiguousarray(pressures, np.float64)
+        if p.shape != (self.B, 2):
+            raise ValueError(f"pressures must be (B = {self.B}, 2), got {p.shape}")
+        check(self.lib.cmpc_sim_set_pressures_host(self._h, p.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
+              "cmpc_sim_set_pressures_host")
+
+    def bind_pressures(self, device_ptr: int = 0):
+        """Bind a device-resident (B, 2) f64 array of [p_in, p_out] (16-byte
+        aligned), read in place by each integrate: the caller may rewrite it
+        between intervals.  0 restores the scalars."""
+        check(self.lib.cmpc_sim_bind_pressures(self._h, ctypes.c_void_p(device_ptr or None)),
+              "cmpc_sim_bind_pressures")
+
+    def get_pressures(self) -> np.ndarray:
+        """(B, 2): the pressures the next integrate uses."""
+        out = np.zeros((self.B, 2))
+        check(self.lib.cmpc_sim_get_pressures(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
+              "cmpc_sim_get_pressures")
+        return out
+
     def restart(self, dt0: float = REF_TS):
         """A new Integrate call: the carried step size starts again at dt0."""
         check(self.lib.cmpc_sim_restart(self._h, dt0), "cmpc_sim_restart")

@@ -160,6 +160,11 @@ struct cmpc_ctx {
   double* own_sc_w = nullptr;
   double* d_yref = nullptr;
   bool yref_dirty = true;
+  // per-scenario boundary pressures of the model (B * 2, [p_in, p_out]) in
+  // force, or null: the scalar arguments; set or bound in the same way
+  // (cmpc_set/bind_scenario_pressures).  The producer reads them (fill_produce).
+  const double* sc_p = nullptr;
+  double* own_sc_p = nullptr;
   int32_t *status = nullptr, *nwsr = nullptr, *ntrace = nullptr;
   char* out_block = nullptr;  // du | status | nwsr in one allocation: one D2H for cmpc_download
   bool out_host = false;      // out_block is page-locked host memory the kernels write in place
@@ -550,7 +555,7 @@ int cmpc_destroy(cmpc_ctx* c) {
                   c->out_host ? nullptr : c->out_block,
                   c->own_ws ? c->own_ws : c->ws,
                   c->trace, c->ntrace, c->obs, c->d_obsM,
-                  c->stage, c->own_sc_dy, c->own_sc_limits, c->own_sc_dref, c->own_sc_w, c->d_yref, c->pred_y,
+                  c->stage, c->own_sc_dy, c->own_sc_limits, c->own_sc_dref, c->own_sc_w, c->own_sc_p, c->d_yref, c->pred_y,
                   c->pred_cost,
                   c->pair_cnt};
   for (void* b : bufs)
@@ -992,6 +997,58 @@ int cmpc_get_scenario_constraints(cmpc_ctx* c, double* lo, double* up, double* r
   return 0;
 }
 
+// Per-scenario boundary pressures (include/cmpc.h): B x [p_in, p_out].  The
+// context's are the model's (the producer reads them at each launch), the
+// simulator's the plant's (cmpc_sim_set_pressures, below).
+static int pressures_check(const char* who, const double* p, size_t B) {
+  for (size_t i = 0; i < 2 * B; ++i)
+    if (!std::isfinite(p[i]) || !(p[i] > 0))
+      return fail(std::string(who) + ": scenario " + std::to_string(i / 2) +
+                  ": pressures must be finite and positive");
+  return 0;
+}
+
+int cmpc_check_pressures(int B, const double* pressures) {
+  if (!pressures || B < 1) return fail("cmpc_check_pressures: null array or empty batch");
+  return pressures_check("cmpc_check_pressures", pressures, (size_t)B);
+}
+
+int cmpc_set_scenario_pressures(cmpc_ctx* c, const double* pressures) {
+  if (!c) return fail("null context");
+  if (!pressures) {
+    c->sc_p = nullptr;
+    return 0;
+  }
+  if (pressures_check("cmpc_set_scenario_pressures", pressures, (size_t)c->d.B)) return -1;
+  if (scenario_upload(c, &c->own_sc_p, pressures, 2 * (size_t)c->d.B)) return -1;
+  c->sc_p = c->own_sc_p;
+  return 0;
+}
+
+int cmpc_bind_scenario_pressures(cmpc_ctx* c, const double* pressures_device) {
+  if (!c) return fail("null context");
+  if (pressures_device) {
+    if (!device_ptr_ok(c, pressures_device, sizeof(double) * 2 * (size_t)c->d.B)) {
+      (void)hipGetLastError();  // a failed pointer query is not a later launch's error
+      return fail("cmpc_bind_scenario_pressures: not a device allocation of B * 2 doubles on the context's device");
+    }
+    if (reinterpret_cast<uintptr_t>(pressures_device) % 8)
+      return fail("cmpc_bind_scenario_pressures: misaligned array");
+  }
+  c->sc_p = pressures_device;
+  return 0;
+}
+
+int cmpc_get_scenario_pressures(cmpc_ctx* c, double* pressures) {
+  if (!c || !pressures) return fail("null argument");
+  if (!c->sc_p) return fail("cmpc_get_scenario_pressures: no per-scenario pressures are set");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(pressures, c->sc_p, sizeof(double) * 2 * (size_t)c->d.B, hipMemcpyDeviceToHost,
+                         c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 static int fill_produce(cmpc_ctx* c, const char* who, int plant, double p_in, double p_out,
                         double Ts, const int32_t* input_order, const int32_t* out_idx,
                         ProduceParams* P, int* n_outputs) {
@@ -1020,6 +1077,7 @@ static int fill_produce(cmpc_ctx* c, const char* who, int plant, double p_in, do
   P->off_f = L.off_f; P->off_x = L.off_x; P->off_y = L.off_y;
   P->p_in = p_in;
   P->p_out = p_out;
+  P->pressures = c->sc_p;  // in force: scenario b's pair in place of the two scalars
   P->Ts = Ts;
   for (int s = 0; s < d.S; ++s) {
     for (int k = 0; k < d.nu_tot; ++k) {
@@ -1445,6 +1503,11 @@ struct cmpc_sim {
   double *x = nullptr, *dt = nullptr, *u_full = nullptr, *u_offset = nullptr, *ring = nullptr,
          *scratch = nullptr, *stage = nullptr;  // stage: host-variant staging (B x max(ns, ni, no, nc))
   int32_t* status = nullptr;
+  // per-scenario boundary pressures of the plant (B * 2, [p_in, p_out]) in
+  // force, or null: p_in, p_out above.  The simulator's own copy
+  // (cmpc_sim_set_pressures[_host], allocated on first use) or a bound array
+  const double* pr = nullptr;
+  double* own_pr = nullptr;
   PinnedIO pin_in, pin_out;  // host-array calls: page-locked staging
 };
 
@@ -1507,7 +1570,7 @@ int cmpc_sim_destroy(cmpc_sim* m) {
   if (m->stream) (void)hipStreamSynchronize(m->stream);
   pinned_free(m->pin_in);
   pinned_free(m->pin_out);
-  void* bufs[] = {m->x, m->dt, m->u_full, m->u_offset, m->ring, m->scratch, m->stage, m->status};
+  void* bufs[] = {m->x, m->dt, m->u_full, m->u_offset, m->ring, m->scratch, m->stage, m->status, m->own_pr};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (m->own_stream && m->stream) (void)hipStreamDestroy(m->stream);
@@ -1639,8 +1702,89 @@ int cmpc_sim_integrate(cmpc_sim* m, double t, double t_end, double eps_abs, doub
   P.eps_rel = eps_rel;
   P.p_in = m->p_in;
   P.p_out = m->p_out;
+  if (m->pr) {  // the per-scenario instance reads scenario b's pair at this launch
+    SimParamsP Q;
+    std::memset(&Q, 0, sizeof Q);
+    static_cast<SimParams&>(Q) = P;
+    Q.pressures = m->pr;
+    if (cmpc_launch_sim_pressures(Q, m->plant, m->stream)) return fail("sim launch failed");
+    return check_launch("sim kernel (per-scenario pressures)");
+  }
   if (cmpc_launch_sim(P, m->plant, m->stream)) return fail("sim launch failed");
   return check_launch("sim kernel");
+}
+
+// Per-scenario boundary pressures of the plant (include/cmpc.h)
+static int sim_own_pressures(cmpc_sim* m) {
+  if (!m->own_pr) HIP_TRY(hipMalloc(&m->own_pr, sizeof(double) * 2 * (size_t)m->B));
+  return 0;
+}
+
+int cmpc_sim_set_pressures(cmpc_sim* m, const double* pressures_device) {
+  if (!m) return fail("null simulator");
+  if (!pressures_device) {
+    m->pr = nullptr;
+    return 0;
+  }
+  HIP_TRY(hipSetDevice(m->device));
+  if (sim_own_pressures(m)) return -1;
+  HIP_TRY(hipMemcpyAsync(m->own_pr, pressures_device, sizeof(double) * 2 * (size_t)m->B, hipMemcpyDeviceToDevice,
+                         m->stream));
+  m->pr = m->own_pr;
+  return 0;
+}
+
+int cmpc_sim_set_pressures_host(cmpc_sim* m, const double* pressures) {
+  if (!m) return fail("null simulator");
+  if (!pressures) {
+    m->pr = nullptr;
+    return 0;
+  }
+  if (pressures_check("cmpc_sim_set_pressures_host", pressures, (size_t)m->B)) return -1;
+  HIP_TRY(hipSetDevice(m->device));
+  if (sim_own_pressures(m)) return -1;
+  HIP_TRY(hipMemcpyAsync(m->own_pr, pressures, sizeof(double) * 2 * (size_t)m->B, hipMemcpyHostToDevice,
+                         m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));  // (the host array is free again)
+  m->pr = m->own_pr;
+  return 0;
+}
+
+int cmpc_sim_bind_pressures(cmpc_sim* m, const double* pressures_device) {
+  if (!m) return fail("null simulator");
+  if (pressures_device) {
+    const size_t bytes = sizeof(double) * 2 * (size_t)m->B;
+    hipPointerAttribute_t a;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipPointerGetAttributes(&a, pressures_device) != hipSuccess || a.type != hipMemoryTypeDevice ||
+        a.device != m->device ||
+        (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)pressures_device) == hipSuccess && base &&
+         (uintptr_t)pressures_device + bytes > (uintptr_t)base + size)) {
+      (void)hipGetLastError();  // a failed pointer query is not a later launch's error
+      return fail("cmpc_sim_bind_pressures: not a device allocation of B * 2 doubles on the simulator's device");
+    }
+    // one 16-byte load per scenario
+    if (reinterpret_cast<uintptr_t>(pressures_device) % 16)
+      return fail("cmpc_sim_bind_pressures: the array must be 16-byte aligned");
+  }
+  m->pr = pressures_device;
+  return 0;
+}
+
+int cmpc_sim_get_pressures(cmpc_sim* m, double* pressures) {
+  if (!m || !pressures) return fail("null argument");
+  HIP_TRY(hipSetDevice(m->device));
+  if (!m->pr) {  // the scalars of cmpc_sim_create hold for every scenario
+    for (int b = 0; b < m->B; ++b) {
+      pressures[2 * b] = m->p_in;
+      pressures[2 * b + 1] = m->p_out;
+    }
+    return 0;
+  }
+  HIP_TRY(hipMemcpyAsync(pressures, m->pr, sizeof(double) * 2 * (size_t)m->B, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  return 0;
 }
 
 int cmpc_sim_output(cmpc_sim* m, double* y) {

@@ -314,6 +314,9 @@ struct ProduceParams {
   const double* obs_M;
   double* obs;  // the observer rows (x above, writable)
   int obs_ntot;
+  // per-scenario boundary pressures (cmpc_set/bind_scenario_pressures): B x
+  // [p_in, p_out], scenario b's pair in place of p_in, p_out above, or null
+  const double* pressures;
 };
 
 // Observer kernels (observer.hip)
@@ -421,6 +424,13 @@ struct SimParams {
   int B;
   double t, t_end, eps_abs, eps_rel, p_in, p_out;
 };
+// Per-scenario boundary pressures (cmpc_sim_set/bind_pressures, DESIGN.md
+// §3.14): the sim kernel's per-scenario instances take SimParams and the
+// array.  Its own struct, so that the scalar instances' arguments stay what
+// they are.
+struct SimParamsP : SimParams {
+  const double* pressures;  // B * 2, [p_in, p_out] per scenario, 16-byte aligned
+};
 struct SimInputParams {
   const double* u_control;  // B * nc
   const double* u_offset;   // B * ni
@@ -439,6 +449,7 @@ struct AccumParams {
 };
 int cmpc_launch_accumulate(const AccumParams& P, void* stream);
 int cmpc_launch_sim(const SimParams& P, int plant, void* stream);
+int cmpc_launch_sim_pressures(const SimParamsP& P, int plant, void* stream);  // -1 without the array
 int cmpc_launch_sim_input(const SimInputParams& P, void* stream);
 int cmpc_launch_sim_output(int plant, const double* x, double* y, int B, void* stream);
 

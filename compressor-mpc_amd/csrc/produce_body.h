@@ -175,15 +175,20 @@ __device__ __forceinline__ void produce_row(const ProduceParams& P, double* w, c
 #define PRODUCE_EXP 0
 #endif
   // the scalar plant model, four scenarios side by side: the parallel
-  // plant's two compressors on lanes 0 and 1 of the row, then its tank
+  // plant's two compressors on lanes 0 and 1 of the row, then its tank.
+  // Boundary pressures: scenario b's pair of P.pressures where that is set (a
+  // uniform branch; the linearising lanes of valid rows alone read it), the
+  // batch's scalars otherwise
+  const double* const pp = P.pressures;
   if (PLANT == CMPC_PLANT_PARALLEL) {
     if (PRODUCE_EXP != 1 && valid && l < 2)
-      cmpc_plant::parallel_linearize_part(l, P.p_in, xs, us, A, Bc, Cc, fc, tk);
+      cmpc_plant::parallel_linearize_part(l, pp ? pp[2 * (size_t)b] : P.p_in, xs, us, A, Bc, Cc, fc, tk);
     WAVE_SYNC();
     if (PRODUCE_EXP != 1 && valid && l == 0)
-      cmpc_plant::parallel_linearize_tank(P.p_out, xs, us, A, Cc, fc, tk);
+      cmpc_plant::parallel_linearize_tank(pp ? pp[2 * (size_t)b + 1] : P.p_out, xs, us, A, Cc, fc, tk);
   } else if (PRODUCE_EXP != 1 && valid && l == 0) {
-    cmpc_plant::serial_linearize(P.p_in, P.p_out, xs, us, A, Bc, Cc, fc, false);
+    cmpc_plant::serial_linearize(pp ? pp[2 * (size_t)b] : P.p_in, pp ? pp[2 * (size_t)b + 1] : P.p_out, xs, us, A,
+                                 Bc, Cc, fc, false);
   }
   WAVE_SYNC();
 

@@ -49,8 +49,11 @@ constexpr double dc1 = c1 - 5179.0 / 57600.0, dc3 = c3 - 7571.0 / 16695.0,
 constexpr double kEps = 2.220446049250313e-16;  // numeric_limits<double>::epsilon()
 constexpr int kMaxSteps = 500;                  // odeint max_step_checker default
 
-template <int PLANT>
-__global__ __launch_bounds__(64) void cmpc_sim_kernel(SimParams P) {
+// One scenario per lane.  SCP: the per-scenario boundary pressures of
+// cmpc_sim_set/bind_pressures (SimParamsP::pressures, one 16-byte load per
+// lane) in place of the batch's scalars; nothing else differs.
+template <int PLANT, bool SCP = false, typename PARAMS = SimParams>
+__global__ __launch_bounds__(64) void cmpc_sim_kernel(PARAMS P) {
   using F = PlantF<PLANT>;
   constexpr int N = F::ns, NI = F::ni;
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -68,7 +71,16 @@ __global__ __launch_bounds__(64) void cmpc_sim_kernel(SimParams P) {
   double t = P.t;
   const double t_end = P.t_end;
   int status = 0, steps = 0;
-  F::f(P.p_in, P.p_out, x, u, k1);  // a fresh stepper per interval: initialize
+  double p_in, p_out;
+  if constexpr (SCP) {
+    const double2 pr = reinterpret_cast<const double2*>(P.pressures)[b];
+    p_in = pr.x;
+    p_out = pr.y;
+  } else {
+    p_in = P.p_in;
+    p_out = P.p_out;
+  }
+  F::f(p_in, p_out, x, u, k1);  // a fresh stepper per interval: initialize
   while (t_end - t > kEps) {
     // odeint's max_step_checker: at most 500 steps between two observer calls
     // (every lane leaves the loop even when the step size collapses)
@@ -82,27 +94,27 @@ __global__ __launch_bounds__(64) void cmpc_sim_kernel(SimParams P) {
       double k2[N], k3[N], k4[N], k5[N], k6[N], k7[N], xt[N], xo[N];
 #pragma unroll
       for (int i = 0; i < N; ++i) xt[i] = x[i] + dt * b21 * k1[i];
-      F::f(P.p_in, P.p_out, xt, u, k2);
+      F::f(p_in, p_out, xt, u, k2);
 #pragma unroll
       for (int i = 0; i < N; ++i) xt[i] = x[i] + dt * b31 * k1[i] + dt * b32 * k2[i];
-      F::f(P.p_in, P.p_out, xt, u, k3);
+      F::f(p_in, p_out, xt, u, k3);
 #pragma unroll
       for (int i = 0; i < N; ++i) xt[i] = x[i] + dt * b41 * k1[i] + dt * b42 * k2[i] + dt * b43 * k3[i];
-      F::f(P.p_in, P.p_out, xt, u, k4);
+      F::f(p_in, p_out, xt, u, k4);
 #pragma unroll
       for (int i = 0; i < N; ++i)
         xt[i] = x[i] + dt * b51 * k1[i] + dt * b52 * k2[i] + dt * b53 * k3[i] + dt * b54 * k4[i];
-      F::f(P.p_in, P.p_out, xt, u, k5);
+      F::f(p_in, p_out, xt, u, k5);
 #pragma unroll
       for (int i = 0; i < N; ++i)
         xt[i] = x[i] + dt * b61 * k1[i] + dt * b62 * k2[i] + dt * b63 * k3[i] + dt * b64 * k4[i] +
                 dt * b65 * k5[i];
-      F::f(P.p_in, P.p_out, xt, u, k6);
+      F::f(p_in, p_out, xt, u, k6);
 #pragma unroll
       for (int i = 0; i < N; ++i)
         xo[i] = x[i] + dt * c1 * k1[i] + dt * c3 * k3[i] + dt * c4 * k4[i] + dt * c5 * k5[i] +
                 dt * c6 * k6[i];
-      F::f(P.p_in, P.p_out, xo, u, k7);
+      F::f(p_in, p_out, xo, u, k7);
       double acc = 0.0;
 #pragma unroll
       for (int i = 0; i < N; ++i) {
@@ -218,6 +230,20 @@ int cmpc_launch_sim(const SimParams& P, int plant, void* stream) {
     hipLaunchKernelGGL(cmpc_sim_kernel<CMPC_PLANT_PARALLEL>, dim3(grid), dim3(64), 0, s, P);
   else if (plant == CMPC_PLANT_SERIAL)
     hipLaunchKernelGGL(cmpc_sim_kernel<CMPC_PLANT_SERIAL>, dim3(grid), dim3(64), 0, s, P);
+  else
+    return -1;
+  return 0;
+}
+
+int cmpc_launch_sim_pressures(const SimParamsP& P, int plant, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (P.B <= 0) return 0;
+  if (!P.pressures) return -1;
+  const int grid = (P.B + 63) / 64;
+  if (plant == CMPC_PLANT_PARALLEL)
+    hipLaunchKernelGGL((cmpc_sim_kernel<CMPC_PLANT_PARALLEL, true, SimParamsP>), dim3(grid), dim3(64), 0, s, P);
+  else if (plant == CMPC_PLANT_SERIAL)
+    hipLaunchKernelGGL((cmpc_sim_kernel<CMPC_PLANT_SERIAL, true, SimParamsP>), dim3(grid), dim3(64), 0, s, P);
   else
     return -1;
   return 0;

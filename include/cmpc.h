@@ -299,6 +299,36 @@ int cmpc_get_scenario_weights(cmpc_ctx* ctx, double* uwt, double* ywt_factor /* 
 int cmpc_scenario_weights_available(const cmpc_dims* dims);
 int cmpc_weight_factor(int ny, const double* ywt, double* lwt);
 
+/* Per-scenario boundary pressures of the controller's model:
+ * B x 2 doubles, [p_in, p_out] of scenario b, the plant's suction and discharge
+ * pressures that cmpc_produce_lin and cmpc_observer_init otherwise take as two
+ * scalars for the whole batch.  Per scenario, not per slot: the sub-controllers
+ * of a scenario model one plant.  While an array is in force
+ *   - cmpc_produce_lin and cmpc_observer_init IGNORE their scalar p_in / p_out
+ *     arguments and linearise scenario b at its own pair;
+ *   - cmpc_observe_step and cmpc_control_step* (the one-launch kernel, its
+ *     role-split pairs and polled completion, and the three-call form alike)
+ *     do the same in place of the scalars cmpc_observer_init kept.
+ * Only the record producer reads it: kernel selection (cmpc_plan), the build,
+ * the solves and cmpc_predict are what they were, and a scenario whose pair
+ * equals the scalars gets bit-identical records.
+ * cmpc_set_scenario_pressures: a host array, every value checked finite and
+ * > 0 (the message names the first bad scenario), copied on the ctx stream into
+ * a buffer the context owns, allocated on first use.  NULL clears: back to the
+ * scalars.
+ * cmpc_bind_scenario_pressures: a device array read in place at each later
+ * launch, so the caller may rewrite it between steps (on the ctx stream, or
+ * ordered with it); checked as cmpc_bind_state checks its pointers, for B*2
+ * doubles, 8-byte aligned; the contents are not checked.  NULL clears.
+ * cmpc_get_scenario_pressures: a host copy of what is in force; -1 if
+ * nothing is.
+ * cmpc_check_pressures (host only): the check of the host setters here and of
+ * cmpc_sim_set_pressures_host on B pairs; -1 with their message. */
+int cmpc_check_pressures(int B, const double* pressures /* B*2, host */);
+int cmpc_set_scenario_pressures(cmpc_ctx* ctx, const double* pressures /* B*2, host */);
+int cmpc_bind_scenario_pressures(cmpc_ctx* ctx, const double* pressures_device /* B*2 */);
+int cmpc_get_scenario_pressures(cmpc_ctx* ctx, double* pressures /* B*2, host */);
+
 /* Hot path. */
 int cmpc_build(cmpc_ctx* ctx);
 /* Kernel selection.  Which kernel an entry point launches is decided by one
@@ -672,7 +702,9 @@ int cmpc_observer_len(const cmpc_ctx* ctx);
  * x_hat = x_init[b] (B x ns), y_old = y_init[b] (B x n_outputs), dx_aug =
  * dx_init (B*S x ntot, or NULL for zero), then the records at x_init (as
  * cmpc_produce_lin, input_order / out_idx as there).  Follow with cmpc_build
- * and cmpc_init_warmstart (InitializeQPProblem). */
+ * and cmpc_init_warmstart (InitializeQPProblem).  p_in, p_out are kept for the
+ * later cmpc_observe_step / cmpc_control_step calls; both are ignored while
+ * per-scenario pressures are in force (cmpc_set/bind_scenario_pressures). */
 int cmpc_observer_init(cmpc_ctx* ctx, int plant, double p_in, double p_out, double Ts,
                        const int32_t* input_order, const int32_t* out_idx,
                        const double* x_init, const double* u_full, const double* y_init,
@@ -778,6 +810,29 @@ double* cmpc_sim_state(cmpc_sim* sim);
 double* cmpc_sim_input(cmpc_sim* sim);
 double* cmpc_sim_step_size(cmpc_sim* sim);
 int32_t* cmpc_sim_status(cmpc_sim* sim);
+/* Per-scenario boundary pressures of the plant: B x 2
+ * doubles, [p_in, p_out] of scenario b, in place of the two scalars given to
+ * cmpc_sim_create.  Each cmpc_sim_integrate reads the array in force at its
+ * launch (one 16-byte load per scenario, in the kernel's per-scenario
+ * instance), so the pressures may change between intervals; a scenario whose
+ * pair equals the scalars integrates bit for bit as it does without.
+ *   cmpc_sim_set_pressures       a device array, copied on the simulator's
+ *                                stream into its own buffer (allocated on
+ *                                first use); not checked
+ *   cmpc_sim_set_pressures_host  a host array, every value checked finite and
+ *                                > 0 (the message names the first bad
+ *                                scenario), then copied
+ *   cmpc_sim_bind_pressures      a device array read in place (16-byte
+ *                                aligned, on the simulator's device); the
+ *                                caller may rewrite it between intervals; not
+ *                                checked
+ *   cmpc_sim_get_pressures       a host copy of what is in force (the scalars,
+ *                                repeated, when no array is)
+ * NULL restores the scalars of cmpc_sim_create in all three. */
+int cmpc_sim_set_pressures(cmpc_sim* sim, const double* pressures_device /* B*2 */);
+int cmpc_sim_set_pressures_host(cmpc_sim* sim, const double* pressures /* B*2, host */);
+int cmpc_sim_bind_pressures(cmpc_sim* sim, const double* pressures_device /* B*2 */);
+int cmpc_sim_get_pressures(cmpc_sim* sim, double* pressures /* B*2, host */);
 /* NerveCenter::UpdateUOld (nerve_center.h:313-319): u_control (device,
  * B x nu_tot, plant control order) += each sub-controller's first move of its
  * own inputs (du_old after cmpc_iterate; input_order as cmpc_produce_lin). */
@@ -792,7 +847,9 @@ int cmpc_accumulate_moves(cmpc_ctx* ctx, const int32_t* input_order, double* u_c
  * controlled rows out_idx[s] (host, S x ny), the observer tail dx_aug
  * (B*S x naug, or NULL for zeros) and y_prev = y[b][out_idx[s]].
  * x (B x ns), u_full (B x n_inputs), dx_aug and y (B x n_outputs) are DEVICE
- * pointers; the call is asynchronous on the context's stream. */
+ * pointers; the call is asynchronous on the context's stream.  p_in, p_out:
+ * the plant's boundary pressures for the whole batch, ignored while
+ * per-scenario pressures are in force (cmpc_set/bind_scenario_pressures). */
 int cmpc_produce_lin(cmpc_ctx* ctx, int plant, double p_in, double p_out, double Ts,
                      const int32_t* input_order, const int32_t* out_idx, const double* x,
                      const double* u_full, const double* dx_aug, const double* y);
