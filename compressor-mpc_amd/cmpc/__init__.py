@@ -35,7 +35,7 @@ __all__ = ["Context", "ControllerConfig", "SetupFile", "reference_config", "refe
            "CMPC_QP_MAX_NWSR", "CMPC_QP_INFEASIBLE", "CMPC_QP_NOT_PD",
            "CMPC_QP_NONFINITE", "build_pairing_available", "build_pairing_reason", "CMPC_PAIRING_AUTO",
            "CMPC_PAIRING_OFF", "CMPC_PAIRING_ON", "scenario_weights_available", "weight_factor",
-           "CMPC_PLAN_SCENARIO_WEIGHTS"]
+           "CMPC_PLAN_SCENARIO_WEIGHTS", "score_len", "score_fields", "score_check", "score_capture_check"]
 
 
 def layout_of(dims: CmpcDims) -> CmpcLayout:
@@ -76,6 +76,52 @@ def weight_factor(ywt) -> np.ndarray:
     out = np.zeros_like(W)
     check(load_library().cmpc_weight_factor(W.shape[0], dptr(W), dptr(out)), "cmpc_weight_factor")
     return out
+
+
+def score_len(dims: CmpcDims) -> int:
+    """Rows of a QP slot's score record for dims (cmpc_score_len, host only)."""
+    n = load_library().cmpc_score_len(ctypes.byref(dims))
+    check(min(n, 0), "cmpc_score_len")
+    return n
+
+
+def score_fields(dims: CmpcDims) -> dict:
+    """{field name: slice of the record's rows} for dims, from the library's
+    own table (cmpc_score_field, host only).  The record is field-major: a
+    download reshaped to (score_len, B*S) is indexed by these slices."""
+    lib = load_library()
+    out = {}
+    for name in _abi.SCORE_FIELDS:
+        off, cnt = ctypes.c_int(), ctypes.c_int()
+        check(lib.cmpc_score_field(ctypes.byref(dims), name.encode(), ctypes.byref(off), ctypes.byref(cnt)),
+              "cmpc_score_field")
+        out[name] = slice(off.value, off.value + cnt.value)
+    return out
+
+
+def score_check(dims: CmpcDims, n_outputs: int, out_idx, Ts: float, band=None):
+    """The argument check of Context.score_enable without a context (host
+    only); raises with the library's message."""
+    oi = np.ascontiguousarray(out_idx, dtype=np.int32).reshape(-1)
+    if oi.size != dims.S * dims.ny:
+        raise ValueError(f"out_idx must hold S*ny = {dims.S * dims.ny} values, got {oi.size}")
+    bd = None
+    if band is not None:
+        bd = np.ascontiguousarray(band, dtype=np.float64).reshape(-1)
+        if bd.size != dims.S * dims.ny:
+            raise ValueError(f"band must hold S*ny = {dims.S * dims.ny} values, got {bd.size}")
+    check(load_library().cmpc_score_check(ctypes.byref(dims), int(n_outputs), iptr(oi), float(Ts),
+                                          dptr(bd) if bd is not None else None), "cmpc_score_check")
+    return oi, bd
+
+
+def score_capture_check(dims: CmpcDims, scenarios, t_cap: int) -> np.ndarray:
+    """The argument check of Context.score_capture without a context (host
+    only); raises with the library's message."""
+    sel = np.ascontiguousarray(scenarios, dtype=np.int32).reshape(-1)
+    check(load_library().cmpc_score_capture_check(ctypes.byref(dims), int(sel.size), iptr(sel), int(t_cap)),
+          "cmpc_score_capture_check")
+    return sel
 
 
 def predict_available(dims: CmpcDims) -> bool:
@@ -659,6 +705,70 @@ class Context:
         """Device addresses of (y_pred, cost); (0, 0) before the first predict."""
         return (self.lib.cmpc_prediction_device(self._h) or 0,
                 self.lib.cmpc_prediction_cost_device(self._h) or 0)
+
+    # -- closed-loop performance indices (include/cmpc.h, cmpc_score_*) -----
+    def score_fields(self) -> dict:
+        """{field name: slice of the record's rows} (score_fields(dims))."""
+        return score_fields(self.dims)
+
+    def score_enable(self, n_outputs: int, out_idx=None, Ts: float = 0.05, band=None):
+        """Keep a running record of closed-loop indices per QP slot.  out_idx
+        (S, ny): the plant output of each controlled output in the y of
+        score_step (default cfg.out_idx); band (S, ny) settling bands or None
+        for 0.  Allocates the record and resets it."""
+        oi = np.asarray(self.cfg.out_idx if out_idx is None else out_idx)[:, :self.cfg.ny]
+        oi, bd = score_check(self.dims, n_outputs, oi, Ts, band)
+        check(self.lib.cmpc_score_enable(self._h, int(n_outputs), iptr(oi), float(Ts),
+                                         dptr(bd) if bd is not None else None), "cmpc_score_enable")
+        self._score_nout = int(n_outputs)
+
+    def score_bind(self, device_ptr: int = 0):
+        """Keep the record in a device buffer of score_len * B*S f64 (0: the
+        context's own).  The buffer is taken as it is: follow with score_reset."""
+        check(self.lib.cmpc_score_bind(self._h, ctypes.c_void_p(device_ptr or None)), "cmpc_score_bind")
+
+    def score_capture(self, scenarios=(), t_cap: int = 0):
+        """Also record rows [y | u_control | x] of the chosen scenarios for the
+        first t_cap steps after a reset; an empty list turns it off."""
+        sel = score_capture_check(self.dims, scenarios, t_cap)
+        check(self.lib.cmpc_score_capture(self._h, int(sel.size), iptr(sel), int(t_cap)), "cmpc_score_capture")
+        self._score_sel, self._score_tcap = int(sel.size), int(t_cap) if sel.size else 0
+
+    def score_bind_capture(self, device_ptr: int = 0):
+        """Put the captured rows into a device buffer of t_cap * n_sel * width
+        f64 (0: the context's own)."""
+        check(self.lib.cmpc_score_bind_capture(self._h, ctypes.c_void_p(device_ptr or None)),
+              "cmpc_score_bind_capture")
+
+    def score_reset(self):
+        check(self.lib.cmpc_score_reset(self._h), "cmpc_score_reset")
+
+    def score_step(self, y_ptr: int, target_ptr: int = 0, plant_status_ptr: int = 0, u_control_ptr: int = 0,
+                   x_ptr: int = 0):
+        """Score the last solve's results against the measured outputs at y_ptr
+        (device, (B, n_outputs)); the other device pointers are optional
+        (cmpc_score_step).  Asynchronous on the context's stream."""
+        vp = lambda p: ctypes.c_void_p(p or None)
+        check(self.lib.cmpc_score_step(self._h, vp(y_ptr), vp(target_ptr), vp(plant_status_ptr), vp(u_control_ptr),
+                                       vp(x_ptr)), "cmpc_score_step")
+
+    def score_download(self) -> np.ndarray:
+        """(score_len, B*S): the record in force, field-major."""
+        out = np.zeros((score_len(self.dims), self.nqp))
+        check(self.lib.cmpc_score_download(self._h, dptr(out)), "cmpc_score_download")
+        return out
+
+    def score_download_capture(self):
+        """(rows (t_cap, n_sel, n_outputs + nu_tot + ns), steps recorded)."""
+        w = self._score_nout + self.cfg.nu_tot + self.cfg.ns
+        rows = np.zeros((getattr(self, "_score_tcap", 0), getattr(self, "_score_sel", 0), w))
+        n = np.zeros(1, np.int32)
+        check(self.lib.cmpc_score_download_capture(self._h, dptr(rows) if rows.size else None, iptr(n)),
+              "cmpc_score_download_capture")
+        return rows, int(n[0])
+
+    def score_disable(self):
+        check(self.lib.cmpc_score_disable(self._h), "cmpc_score_disable")
 
     # -- results ---------------------------------------------------------
     def download(self):

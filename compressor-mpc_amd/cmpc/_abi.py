@@ -153,7 +153,16 @@ EXPORTS = (
     "cmpc_set_scenario_pressures", "cmpc_bind_scenario_pressures", "cmpc_get_scenario_pressures",
     "cmpc_sim_set_pressures", "cmpc_sim_set_pressures_host", "cmpc_sim_bind_pressures",
     "cmpc_sim_get_pressures", "cmpc_check_pressures",
+    "cmpc_score_len", "cmpc_score_field", "cmpc_score_check", "cmpc_score_capture_check",
+    "cmpc_score_enable", "cmpc_score_bind", "cmpc_score_capture", "cmpc_score_bind_capture",
+    "cmpc_score_reset", "cmpc_score_step", "cmpc_score_download", "cmpc_score_download_capture",
+    "cmpc_score_disable",
 )
+
+# the fields of a slot's score record, in the record's order (cmpc_score_field
+# gives each one's rows; include/cmpc.h has the table)
+SCORE_FIELDS = ("n", "ise", "iae", "peak", "last_out", "j_track", "j_move", "tv", "sat_bound", "sat_rate",
+                "n_fail", "nwsr_sum", "plant_fail_step")
 
 _lib = None
 
@@ -305,6 +314,19 @@ def load_library(path: str = LIB_PATH):
         "cmpc_sim_bind_pressures": ([c_void, c_void], ctypes.c_int),
         "cmpc_sim_get_pressures": ([c_void, P(dbl)], ctypes.c_int),
         "cmpc_check_pressures": ([ctypes.c_int, P(dbl)], ctypes.c_int),
+        "cmpc_score_len": ([P(CmpcDims)], ctypes.c_int),
+        "cmpc_score_field": ([P(CmpcDims), ctypes.c_char_p, P(ctypes.c_int), P(ctypes.c_int)], ctypes.c_int),
+        "cmpc_score_check": ([P(CmpcDims), ctypes.c_int, P(i32), dbl, P(dbl)], ctypes.c_int),
+        "cmpc_score_capture_check": ([P(CmpcDims), ctypes.c_int, P(i32), ctypes.c_int], ctypes.c_int),
+        "cmpc_score_enable": ([c_void, ctypes.c_int, P(i32), dbl, P(dbl)], ctypes.c_int),
+        "cmpc_score_bind": ([c_void, c_void], ctypes.c_int),
+        "cmpc_score_capture": ([c_void, ctypes.c_int, P(i32), ctypes.c_int], ctypes.c_int),
+        "cmpc_score_bind_capture": ([c_void, c_void], ctypes.c_int),
+        "cmpc_score_reset": ([c_void], ctypes.c_int),
+        "cmpc_score_step": ([c_void, c_void, c_void, c_void, c_void, c_void], ctypes.c_int),
+        "cmpc_score_download": ([c_void, P(dbl)], ctypes.c_int),
+        "cmpc_score_download_capture": ([c_void, P(dbl), P(i32)], ctypes.c_int),
+        "cmpc_score_disable": ([c_void], ctypes.c_int),
         "cmpc_qp_solve_batch": ([ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(dbl),
                                  P(dbl), P(dbl), P(dbl), P(dbl), P(dbl), P(u32), ctypes.c_int,
                                  P(dbl), P(i32), P(i32), P(u32), P(ctypes.c_uint8), P(i32)],

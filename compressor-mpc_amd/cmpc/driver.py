@@ -96,6 +96,7 @@ class ClosedLoop:
         torch.cuda.init()
         dev = torch.device("cuda", device)
         self.cfg, self.K, self.Ts, self.dev = cfg, K, Ts, dev
+        self.arrays = arrays
         self.p_in, self.p_out = p_in, p_out
         B = x0.shape[0]
         self.B, S = B, cfg.S
@@ -110,6 +111,8 @@ class ClosedLoop:
                            np.zeros(B * S, np.uint32))
         for s in range(S):
             self.ctx.set_observer(s, M[s])
+        self._scores = False    # enable_scores: closed-loop indices per QP slot
+        self._dy_ref = None     # the setpoint offsets in force, (B*S, ny) host
         if y_offset is not None:
             self.set_setpoints(y_offset)
         if limits is not None:
@@ -149,11 +152,14 @@ class ClosedLoop:
         output, in force from the next build on; None removes them."""
         if y_offset is None:
             self.ctx.set_scenario_reference(None)
+            self._dy_ref = self._score_sched = None
             return
         y_offset = np.asarray(y_offset, dtype=np.float64)
         if y_offset.ndim != 2 or y_offset.shape[0] != self.B:
             raise ValueError(f"y_offset must be (B = {self.B}, n_outputs), got {y_offset.shape}")
-        self.ctx.set_scenario_reference(scenario_reference_offsets(self.cfg, y_offset))
+        self._dy_ref = scenario_reference_offsets(self.cfg, y_offset)
+        self._score_sched = None
+        self.ctx.set_scenario_reference(self._dy_ref)
 
     def set_weights_per_scenario(self, uwt, ywt):
         """Per-scenario weights for a tuning sweep: uwt (B, S, nu, nu) and ywt
@@ -187,6 +193,7 @@ class ClosedLoop:
         (Context.bind_scenario_reference_profile).  Independent of
         set_setpoints; the two add."""
         torch = self.torch
+        self._score_sched = None
         if schedule is None:
             self.ctx.bind_scenario_reference_profile(0)
             self._sp_sched = self._sp_window = None
@@ -284,6 +291,87 @@ class ClosedLoop:
             if sch is not None:
                 self._bound_pressures(model).copy_(sch[:, min(self.k, sch.shape[1] - 1), :])
 
+    def enable_scores(self, band=None, capture=None, capture_steps: int = 0):
+        """Keep closed-loop performance indices of every QP slot on the device
+        (Context.score_*, include/cmpc.h has the field table): each step then
+        scores its instant in one small launch after the moves are
+        accumulated and before the plant integrates, against y_ref[s][0] +
+        dy_ref[q] (+ schedule[b][min(k, T - 1)][out_idx[s]] with a setpoint
+        schedule in force: the setpoint of the measured instant).  band: (S,
+        ny) settling bands per controlled output, None for 0.  capture: a list
+        of scenarios whose trajectories [y | u_ctrl | x] of the first
+        capture_steps instants are kept too (captured()).  initialize resets
+        the record.  Arguments are refused before anything is allocated."""
+        from . import score_capture_check, score_check
+        n_out = self.sim.no
+        oi = np.asarray(self.cfg.out_idx)[:, :self.cfg.ny]
+        if band is not None:
+            band = np.asarray(band, dtype=np.float64)
+            if band.shape != (self.cfg.S, self.cfg.ny):
+                raise ValueError(f"band must be (S = {self.cfg.S}, ny = {self.cfg.ny}), got {band.shape}")
+            if not np.isfinite(band).all() or (band < 0).any():
+                raise ValueError("band must be finite and >= 0")
+        score_check(self.ctx.dims, n_out, oi, self.Ts, band)
+        sel = []
+        if capture is not None and len(capture):
+            sel = np.asarray(capture)
+            if sel.ndim != 1 or not np.issubdtype(sel.dtype, np.integer):
+                raise ValueError(f"capture must be a list of scenario indices, got {sel!r}")
+            if len(set(sel.tolist())) != sel.size or sel.min() < 0 or sel.max() >= self.B:
+                raise ValueError(f"capture indices must be distinct and inside [0, B = {self.B})")
+            if int(capture_steps) < 1:
+                raise ValueError("capture_steps must be >= 1 with a capture list")
+            score_capture_check(self.ctx.dims, sel, capture_steps)
+        self.ctx.score_enable(n_out, oi, self.Ts, band)
+        self.ctx.score_capture(sel, int(capture_steps) if len(sel) else 0)
+        self._scores = True
+        self._score_sched = None   # (B, S, T, ny) device: the targets per schedule row, made at first use
+        self._score_target = self.torch.zeros(self.B * self.cfg.S, self.cfg.ny, dtype=self.torch.float64,
+                                              device=self.dev)
+
+    def _score_step(self, y):
+        """The instant's indices (enable_scores): one launch on the step's stream."""
+        tgt = 0
+        if self._sp_sched is not None:
+            if self._score_sched is None:
+                S, ny = self.cfg.S, self.cfg.ny
+                base = np.stack([np.asarray(self.arrays.y_ref[s], dtype=np.float64).reshape(self.cfg.p, ny)[0]
+                                 for s in range(S)])
+                base = np.broadcast_to(base, (self.B, S, ny)).copy()   # y_ref[s][0]
+                if self._dy_ref is not None:
+                    base = base + self._dy_ref.reshape(self.B, S, ny)
+                base = self.torch.from_numpy(base).to(self.dev)
+                self._score_sched = (base[:, :, None, :] + self._sp_sched).contiguous()
+            T = self._score_sched.shape[2]
+            self._score_target.copy_(self._score_sched[:, :, min(self.k, T - 1), :].reshape(self._score_target.shape))
+            tgt = self._score_target.data_ptr()
+        self.ctx.score_step(y.data_ptr(), tgt, self.sim.status_ptr() or 0,
+                            self.u_ctrl.data_ptr(), self.sim.state_ptr())
+
+    def scores(self) -> dict:
+        """The indices so far: {field: (B, S) or (B, S, rows) host array} for the
+        fields of include/cmpc.h's table, plus settling_time = (last_out + 1)
+        Ts per controlled output."""
+        rec = self.ctx.score_download()
+        S = self.cfg.S
+        out = {}
+        for name, sl in self.ctx.score_fields().items():
+            a = rec[sl].reshape(sl.stop - sl.start, self.B, S).transpose(1, 2, 0)
+            scalar = name in ("n", "j_track", "j_move", "n_fail", "nwsr_sum", "plant_fail_step")
+            out[name] = np.ascontiguousarray(a[:, :, 0] if scalar else a)
+        out["settling_time"] = (out["last_out"] + 1.0) * self.Ts
+        return out
+
+    def captured(self):
+        """(t (n,), y (n, n_sel, n_outputs), u (n, n_sel, nu_tot), x (n, n_sel,
+        ns)) of the scenarios given to enable_scores(capture=...), in that
+        order, for the n instants recorded so far."""
+        rows, n = self.ctx.score_download_capture()
+        no, nu = self.sim.no, self.cfg.nu_tot
+        rows = rows[:n]
+        return (np.arange(n) * self.Ts, np.ascontiguousarray(rows[:, :, :no]),
+                np.ascontiguousarray(rows[:, :, no:no + nu]), np.ascontiguousarray(rows[:, :, no + nu:]))
+
     def initialize(self, dx_init=None):
         """SimulationSystem(x0, u_offset) + NerveCenter::Initialize(x0, 0,
         u_offset, y(x0), dx_init): the observers' state, the records at x0,
@@ -301,6 +389,8 @@ class ClosedLoop:
         self.ctx.build()
         self.ctx.init_warmstart()
         self.t_seg, self.seg_step = 0.0, 0   # integrate_const's start time and step count
+        if self._scores:
+            self.ctx.score_reset()
 
     def step(self, trace: bool = False, predict: bool = False):
         """One sampling instant: returns (t, y) of the instant; the plant has
@@ -335,6 +425,8 @@ class ClosedLoop:
         self.ctx.observe_apply()
         check(self.ctx.lib.cmpc_accumulate_moves(self.ctx._h, iptr(self.io),
                                                  self.torch_ptr(self.u_ctrl)), "cmpc_accumulate_moves")
+        if self._scores:
+            self._score_step(y)
         # SetInput(u) through the delay line, then the plant over [t, t + Ts];
         # at the end of a segment's Integrate call: SetOffset and a new call
         self.sim.set_input(self.u_ctrl)

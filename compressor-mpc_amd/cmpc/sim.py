@@ -160,3 +160,7 @@ class PlantSimulator:
 
     def input_ptr(self) -> int:
         return self.lib.cmpc_sim_input(self._h)
+
+    def status_ptr(self) -> int:
+        """Device address of the (B,) int32 status words (cmpc_sim_status)."""
+        return self.lib.cmpc_sim_status(self._h)

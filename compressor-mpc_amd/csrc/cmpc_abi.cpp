@@ -220,6 +220,19 @@ struct cmpc_ctx {
   bool pred_done = false;
   bool pred_built = false;  // a build has run
   const char* pred_stale = nullptr;
+  // closed-loop performance indices (cmpc_score_*): everything is allocated by
+  // cmpc_score_enable / cmpc_score_capture and freed by cmpc_score_disable;
+  // score_rec / score_cap are the buffers in force (own or bound)
+  bool score_on = false;
+  int score_nout = 0;
+  double score_Ts = 0;
+  int64_t score_k = 0;             // steps since the last reset
+  double* score_band = nullptr;    // S * ny
+  int32_t* score_oi = nullptr;     // S * ny
+  double *score_own = nullptr, *score_rec = nullptr;
+  int score_nsel = 0, score_tcap = 0;
+  int32_t* score_map = nullptr;    // B: capture column or -1
+  double *score_cap_own = nullptr, *score_cap = nullptr;
   // timing
   int timing = 0;  // bit k: kernel k (CMPC_KERNEL_*) is timed
   int timing_stride = 1;                        // time every stride-th launch
@@ -557,7 +570,7 @@ int cmpc_destroy(cmpc_ctx* c) {
                   c->trace, c->ntrace, c->obs, c->d_obsM,
                   c->stage, c->own_sc_dy, c->own_sc_limits, c->own_sc_dref, c->own_sc_w, c->own_sc_p, c->d_yref, c->pred_y,
                   c->pred_cost,
-                  c->pair_cnt};
+                  c->pair_cnt, c->score_band, c->score_oi, c->score_own, c->score_map, c->score_cap_own};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -2487,6 +2500,273 @@ int cmpc_download_prediction(cmpc_ctx* c, double* y_pred, double* cost) {
                            c->stream));
   if (cost) HIP_TRY(hipMemcpyAsync(cost, c->pred_cost, sizeof(double) * n * 2, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// Closed-loop performance indices (include/cmpc.h, score.hip).
+static const struct {
+  const char* name;
+  int ScoreFields::*row;
+  int per;  // rows: 0 one, 1 ny, 2 nu
+} kScoreFields[] = {
+    {"n", &ScoreFields::n, 0},           {"ise", &ScoreFields::ise, 1},
+    {"iae", &ScoreFields::iae, 1},       {"peak", &ScoreFields::peak, 1},
+    {"last_out", &ScoreFields::last_out, 1}, {"j_track", &ScoreFields::j_track, 0},
+    {"j_move", &ScoreFields::j_move, 0}, {"tv", &ScoreFields::tv, 2},
+    {"sat_bound", &ScoreFields::sat_bound, 2}, {"sat_rate", &ScoreFields::sat_rate, 2},
+    {"n_fail", &ScoreFields::n_fail, 0}, {"nwsr_sum", &ScoreFields::nwsr_sum, 0},
+    {"plant_fail_step", &ScoreFields::plant_fail_step, 0},
+};
+
+int cmpc_score_len(const cmpc_dims* dims) {
+  cmpc_layout L;
+  if (!dims) return fail("null argument");
+  if (layout_of(dims, &L)) return -1;
+  return cmpc_score_fields(dims->ny, dims->nu).len;
+}
+
+int cmpc_score_field(const cmpc_dims* dims, const char* name, int* offset, int* count) {
+  cmpc_layout L;
+  if (!dims || !name) return fail("null argument");
+  if (layout_of(dims, &L)) return -1;
+  const ScoreFields F = cmpc_score_fields(dims->ny, dims->nu);
+  for (const auto& f : kScoreFields)
+    if (!std::strcmp(name, f.name)) {
+      if (offset) *offset = F.*(f.row);
+      if (count) *count = f.per == 0 ? 1 : f.per == 1 ? dims->ny : dims->nu;
+      return 0;
+    }
+  return fail(std::string("cmpc_score_field: no field named '") + name + "'");
+}
+
+int cmpc_score_check(const cmpc_dims* dims, int n_outputs, const int32_t* out_idx, double Ts, const double* band) {
+  cmpc_layout L;
+  if (!dims || !out_idx) return fail("cmpc_score_enable: null argument");
+  if (layout_of(dims, &L)) return -1;
+  if (!cmpc_score_instance(dims->ny, dims->nu))
+    return fail("cmpc_score_enable: score kernel not instantiated for these dimensions (ny, nu)");
+  if (n_outputs < 1) return fail("cmpc_score_enable: n_outputs must be >= 1");
+  if (!std::isfinite(Ts) || Ts < 0) return fail("cmpc_score_enable: Ts must be finite and >= 0");
+  for (int i = 0; i < dims->S * dims->ny; ++i) {
+    if (out_idx[i] < 0 || out_idx[i] >= n_outputs)
+      return fail("cmpc_score_enable: sub-controller " + std::to_string(i / dims->ny) +
+                  ": out_idx outside [0, n_outputs)");
+    if (band && (!std::isfinite(band[i]) || band[i] < 0))
+      return fail("cmpc_score_enable: sub-controller " + std::to_string(i / dims->ny) +
+                  ": band must be finite and >= 0");
+  }
+  return 0;
+}
+
+int cmpc_score_capture_check(const cmpc_dims* dims, int n_sel, const int32_t* scenarios, int t_cap) {
+  cmpc_layout L;
+  if (!dims) return fail("cmpc_score_capture: null argument");
+  if (layout_of(dims, &L)) return -1;
+  if (n_sel < 0) return fail("cmpc_score_capture: n_sel must be >= 0");
+  if (n_sel == 0) return 0;
+  if (!scenarios) return fail("cmpc_score_capture: null scenario list");
+  if (t_cap < 1) return fail("cmpc_score_capture: t_cap must be >= 1");
+  if (n_sel > dims->B) return fail("cmpc_score_capture: more scenarios than the batch holds");
+  for (int i = 0; i < n_sel; ++i) {
+    if (scenarios[i] < 0 || scenarios[i] >= dims->B)
+      return fail("cmpc_score_capture: scenario " + std::to_string(scenarios[i]) + " outside [0, B)");
+    for (int j = 0; j < i; ++j)
+      if (scenarios[j] == scenarios[i])
+        return fail("cmpc_score_capture: scenario " + std::to_string(scenarios[i]) + " given twice");
+  }
+  return 0;
+}
+
+static int score_cap_width(const cmpc_ctx* c) { return c->score_nout + c->d.nu_tot + c->d.ns; }
+
+static void score_capture_free(cmpc_ctx* c) {
+  if (c->score_map) (void)hipFree(c->score_map);
+  if (c->score_cap_own) (void)hipFree(c->score_cap_own);
+  c->score_map = nullptr;
+  c->score_cap_own = c->score_cap = nullptr;
+  c->score_nsel = c->score_tcap = 0;
+}
+
+int cmpc_score_reset(cmpc_ctx* c) {
+  if (!c) return fail("null context");
+  if (!c->score_on) return fail("cmpc_score_reset: scoring is not enabled (cmpc_score_enable)");
+  HIP_TRY(hipSetDevice(c->device));
+  if (cmpc_launch_score_reset(c->score_rec, c->nqp, c->d.ny, c->d.nu, c->stream))
+    return fail("cmpc_score_reset: launch failed");
+  if (check_launch("score reset kernel")) return -1;
+  if (c->score_cap_own && c->score_cap == c->score_cap_own)
+    HIP_TRY(hipMemsetAsync(c->score_cap_own, 0,
+                           sizeof(double) * (size_t)c->score_tcap * c->score_nsel * score_cap_width(c), c->stream));
+  c->score_k = 0;
+  return 0;
+}
+
+int cmpc_score_enable(cmpc_ctx* c, int n_outputs, const int32_t* out_idx, double Ts, const double* band) {
+  if (!c) return fail("null context");
+  if (cmpc_score_check(&c->d, n_outputs, out_idx, Ts, band)) return -1;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t m = (size_t)c->d.S * c->d.ny;
+  if (c->score_on && n_outputs != c->score_nout) score_capture_free(c);  // (its row width has changed)
+  if (!c->score_band) HIP_TRY(hipMalloc(&c->score_band, sizeof(double) * m));
+  if (!c->score_oi) HIP_TRY(hipMalloc(&c->score_oi, sizeof(int32_t) * m));
+  if (!c->score_own)
+    HIP_TRY(hipMalloc(&c->score_own, sizeof(double) * (size_t)cmpc_score_fields(c->d.ny, c->d.nu).len * c->nqp));
+  if (ensure_yref(c)) return -1;
+  std::vector<double> hb(m, 0.0);
+  if (band) std::copy(band, band + m, hb.begin());
+  HIP_TRY(hipMemcpyAsync(c->score_band, hb.data(), sizeof(double) * m, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(c->score_oi, out_idx, sizeof(int32_t) * m, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (!c->score_rec) c->score_rec = c->score_own;
+  c->score_nout = n_outputs;
+  c->score_Ts = Ts;
+  c->score_on = true;
+  return cmpc_score_reset(c);
+}
+
+int cmpc_score_bind(cmpc_ctx* c, double* scores_device) {
+  if (!c) return fail("null context");
+  if (!c->score_on) return fail("cmpc_score_bind: scoring is not enabled (cmpc_score_enable)");
+  if (scores_device) {
+    const size_t bytes = sizeof(double) * (size_t)cmpc_score_fields(c->d.ny, c->d.nu).len * c->nqp;
+    if (!device_ptr_ok(c, scores_device, bytes)) {
+      (void)hipGetLastError();  // a failed pointer query is not a later launch's error
+      return fail("cmpc_score_bind: not a device allocation of len * nqp doubles on the context's device");
+    }
+    if (reinterpret_cast<uintptr_t>(scores_device) % 8) return fail("cmpc_score_bind: misaligned array");
+  }
+  c->score_rec = scores_device ? scores_device : c->score_own;
+  return 0;
+}
+
+int cmpc_score_capture(cmpc_ctx* c, int n_sel, const int32_t* scenarios, int t_cap) {
+  if (!c) return fail("null context");
+  if (!c->score_on) return fail("cmpc_score_capture: scoring is not enabled (cmpc_score_enable)");
+  if (cmpc_score_capture_check(&c->d, n_sel, scenarios, t_cap)) return -1;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  score_capture_free(c);
+  if (n_sel == 0) return 0;
+  std::vector<int32_t> map((size_t)c->d.B, -1);
+  for (int i = 0; i < n_sel; ++i) map[scenarios[i]] = i;
+  const size_t rows = sizeof(double) * (size_t)t_cap * n_sel * score_cap_width(c);
+  HIP_TRY(hipMalloc(&c->score_map, sizeof(int32_t) * map.size()));
+  HIP_TRY(hipMalloc(&c->score_cap_own, rows));
+  HIP_TRY(hipMemcpyAsync(c->score_map, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(c->score_cap_own, 0, rows, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->score_cap = c->score_cap_own;
+  c->score_nsel = n_sel;
+  c->score_tcap = t_cap;
+  return 0;
+}
+
+int cmpc_score_bind_capture(cmpc_ctx* c, double* rows_device) {
+  if (!c) return fail("null context");
+  if (!c->score_on || !c->score_nsel)
+    return fail("cmpc_score_bind_capture: no capture is enabled (cmpc_score_capture)");
+  if (rows_device) {
+    const size_t bytes = sizeof(double) * (size_t)c->score_tcap * c->score_nsel * score_cap_width(c);
+    if (!device_ptr_ok(c, rows_device, bytes)) {
+      (void)hipGetLastError();  // a failed pointer query is not a later launch's error
+      return fail("cmpc_score_bind_capture: not a device allocation of t_cap * n_sel * width doubles on the "
+                  "context's device");
+    }
+    if (reinterpret_cast<uintptr_t>(rows_device) % 8) return fail("cmpc_score_bind_capture: misaligned array");
+  }
+  c->score_cap = rows_device ? rows_device : c->score_cap_own;
+  return 0;
+}
+
+int cmpc_score_step(cmpc_ctx* c, const double* y, const double* target, const int32_t* plant_status,
+                    const double* u_control, const double* x) {
+  if (!c) return fail("null context");
+  if (!c->score_on) return fail("cmpc_score_step: scoring is not enabled (cmpc_score_enable)");
+  if (!y) return fail("cmpc_score_step: null y");
+  if (!c->last_solve) return fail("cmpc_score_step: no solve has run (cmpc_iterate, cmpc_step, cmpc_control_step)");
+  if (c->score_k >= INT32_MAX) return fail("cmpc_score_step: step count overflow (cmpc_score_reset)");
+  if (ensure_cfg(c)) return -1;
+  HIP_TRY(hipSetDevice(c->device));
+  if (!target && ensure_yref(c)) return -1;  // (allocated by cmpc_score_enable; a copy when the references changed)
+  ScoreParams P;
+  std::memset(&P, 0, sizeof P);
+  P.rec = c->score_rec;
+  P.y = y;
+  P.target = target;
+  P.cfg = c->cfg;
+  P.yref = c->d_yref;
+  P.dy_ref = c->sc_dy;
+  P.sc_w = c->sc_w;
+  P.du = c->du;  // (page-locked host memory up to CMPC_HOST_OUT_MAX_QP slots: its device address)
+  P.status = c->status;
+  P.nwsr = c->nwsr;
+  P.ws = c->ws;
+  P.plant_status = plant_status;
+  P.out_idx = c->score_oi;
+  P.band = c->score_band;
+  if (c->score_nsel) {
+    P.cap_map = c->score_map;
+    P.cap = c->score_cap;
+    P.u_control = u_control;
+    P.x = x;
+    P.n_sel = c->score_nsel;
+    P.t_cap = c->score_tcap;
+    P.cap_w = score_cap_width(c);
+  }
+  P.n_out = c->score_nout;
+  P.nu_tot = c->d.nu_tot;
+  P.ns = c->d.ns;
+  P.nqp = c->nqp;
+  P.S = c->d.S;
+  P.p = c->d.p;
+  P.nV = c->L.nV;
+  P.k = (int)c->score_k;
+  P.Ts = c->score_Ts;
+  P.co = c->co;
+  if (cmpc_launch_score(P, c->d.ny, c->d.nu, c->stream)) return plan_mismatch("score");
+  if (check_launch("score kernel")) return -1;
+  c->score_k++;
+  return 0;
+}
+
+int cmpc_score_download(cmpc_ctx* c, double* scores) {
+  if (!c || !scores) return fail("null argument");
+  if (!c->score_on) return fail("cmpc_score_download: scoring is not enabled (cmpc_score_enable)");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(scores, c->score_rec,
+                         sizeof(double) * (size_t)cmpc_score_fields(c->d.ny, c->d.nu).len * c->nqp,
+                         hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int cmpc_score_download_capture(cmpc_ctx* c, double* rows, int32_t* n_rows) {
+  if (!c) return fail("null context");
+  if (!c->score_on || !c->score_nsel)
+    return fail("cmpc_score_download_capture: no capture is enabled (cmpc_score_capture)");
+  HIP_TRY(hipSetDevice(c->device));
+  if (rows)
+    HIP_TRY(hipMemcpyAsync(rows, c->score_cap,
+                           sizeof(double) * (size_t)c->score_tcap * c->score_nsel * score_cap_width(c),
+                           hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (n_rows) *n_rows = (int32_t)std::min<int64_t>(c->score_k, c->score_tcap);
+  return 0;
+}
+
+int cmpc_score_disable(cmpc_ctx* c) {
+  if (!c) return fail("null context");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  score_capture_free(c);
+  if (c->score_band) (void)hipFree(c->score_band);
+  if (c->score_oi) (void)hipFree(c->score_oi);
+  if (c->score_own) (void)hipFree(c->score_own);
+  c->score_band = nullptr;
+  c->score_oi = nullptr;
+  c->score_own = c->score_rec = nullptr;
+  c->score_on = false;
+  c->score_k = 0;
   return 0;
 }
 

@@ -269,6 +269,65 @@ struct RefshiftParams {
 // one QP per 16-lane row, four per one-wave workgroup; -1: no instance
 int cmpc_launch_refshift(const RefshiftParams& P, const cmpc_dims& d, void* stream);
 
+// Closed-loop performance indices (score.hip, cmpc_score_*):
+// one running record per QP slot, field-major (field row f of slot q at
+// f * nqp + q), all doubles.  The rows of each field, in the record's order;
+// the kernel, the host functions and cmpc_score_field take them from here.
+struct ScoreFields {
+  int n, ise, iae, peak, last_out, j_track, j_move, tv, sat_bound, sat_rate, n_fail, nwsr_sum,
+      plant_fail_step, len;
+};
+__host__ __device__ constexpr ScoreFields cmpc_score_fields(int ny, int nu) {
+  ScoreFields F{};
+  int o = 0;
+  F.n = o; o += 1;
+  F.ise = o; o += ny;
+  F.iae = o; o += ny;
+  F.peak = o; o += ny;
+  F.last_out = o; o += ny;
+  F.j_track = o; o += 1;
+  F.j_move = o; o += 1;
+  F.tv = o; o += nu;
+  F.sat_bound = o; o += nu;
+  F.sat_rate = o; o += nu;
+  F.n_fail = o; o += 1;
+  F.nwsr_sum = o; o += 1;
+  F.plant_fail_step = o; o += 1;
+  F.len = o;
+  return F;
+}
+struct ScoreParams {
+  double* rec;                  // len * nqp running records, field-major
+  const double* y;              // B * n_out measured plant outputs
+  const double* target;         // nqp * ny, or null: y_ref[s][0] + dy_ref[q]
+  const double* cfg;            // S * co.len
+  const double* yref;           // S * p * ny raw references (row 0 is read), with target null
+  const double* dy_ref;         // nqp * ny per-slot setpoint offsets, or null
+  const double* sc_w;           // nqp * (ny*ny + nu*nu) per-slot [L_W' | uwt], or null: the cfg block's
+  const double* du;             // nqp * nV plans (the own first move is read)
+  const int32_t* status;        // nqp
+  const int32_t* nwsr;          // nqp
+  const uint32_t* ws;           // nqp working-set words of the state in force
+  const int32_t* plant_status;  // B simulator status words, or null
+  const int32_t* out_idx;       // S * ny: plant output of each controlled output
+  const double* band;           // S * ny settling bands
+  // trajectory capture: row [y n_out | u_control nu_tot | x ns] of the chosen
+  // scenarios at step k < t_cap, written by the lane of slot s == 0
+  const int32_t* cap_map;       // B: capture column of scenario b or -1; null: capture off
+  double* cap;                  // t_cap * n_sel * cap_w
+  const double* u_control;      // B * nu_tot or null (columns left as they are)
+  const double* x;              // B * ns or null
+  int n_sel, t_cap, cap_w, n_out, nu_tot, ns;
+  int nqp, S, p, nV, k;
+  double Ts;
+  CfgOffsets co;
+};
+bool cmpc_score_instance(int ny, int nu);
+// one lane per QP slot, 64-lane workgroups; -1: no instance for (ny, nu)
+int cmpc_launch_score(const ScoreParams& P, int ny, int nu, void* stream);
+// every field of every slot to 0, last_out and plant_fail_step to -1
+int cmpc_launch_score_reset(double* rec, int nqp, int ny, int nu, void* stream);
+
 // Standalone batched solver (parity / KKT tests).  G (nqp * n * nvo) and d
 // (nqp * nvo) non-null: the Jacobi iteration's map-form solve with g = f + G d
 // (cmpc_qp_solve_batch_map); g is f then.

@@ -554,6 +554,96 @@ double* cmpc_prediction_cost_device(cmpc_ctx* ctx);
 int cmpc_download_prediction(cmpc_ctx* ctx, double* y_pred, double* cost);
 int cmpc_predict_available(const cmpc_dims* dims);
 
+/* Closed-loop performance indices per QP slot (score.hip).
+ *
+ * How well each scenario of a batch did, kept on the device: one small launch
+ * per sampling instant (cmpc_score_step) reads the step's results where the
+ * context holds them and updates a running record per QP slot q = b*S + s.
+ * With e[o] = y[b][out_idx[s][o]] - r[q][o], r = target[q] where a target is
+ * given and y_ref[s][0] + dy_ref[q] otherwise (row 0 of cmpc_set_reference,
+ * dy_ref of cmpc_set/bind_scenario_reference where one is in force), du the
+ * slot's first move of its own inputs, and k the step index (0 after a reset,
+ * counted on the host):
+ *
+ *   field            rows  update at step k
+ *   n                1     += 1
+ *   ise[o]           ny    += (e e) Ts
+ *   iae[o]           ny    += |e| Ts
+ *   peak[o]          ny    max(peak, |e|)
+ *   last_out[o]      ny    k if |e| > band[s][o]; starts at -1: the settling
+ *                          time is (last_out + 1) Ts
+ *   j_track          1     += 1/2 |L_W' e|^2, the realised stage cost in the
+ *                          controller's own weights (the slot's ywt[q] where
+ *                          per-slot weights are in force)
+ *   j_move           1     += 1/2 du' uwt du (uwt[q] likewise)
+ *   tv[c]            nu    += |du[c]|
+ *   sat_bound[c]     nu    += 1 when status == CMPC_QP_OK and the slot's
+ *                          working-set word holds the first move's bound of own
+ *                          input c (bit c, either side)
+ *   sat_rate[c]      nu    the same for its rate row (bit nV + c)
+ *   n_fail           1     += 1 when status != CMPC_QP_OK
+ *   nwsr_sum         1     += nwsr
+ *   plant_fail_step  1     the first k with a non-zero plant status; -1 until then
+ *
+ * All fields are doubles (the counters are exact far beyond any run length),
+ * in this order, cmpc_score_len(dims) = 4 ny + 3 nu + 6 rows in all.  Storage
+ * is field-major: row f of slot q at f*B*S + q.  cmpc_score_field gives a
+ * field's first row and row count by name (-1 for an unknown name); callers
+ * take offsets from it.  The sums are plain FP64 multiplies and adds in the
+ * order written, so a float64 host model reproduces every field but j_track
+ * and j_move (any fixed order) bit for bit.
+ *
+ * cmpc_score_enable: out_idx (host, S*ny) names the plant output of each
+ *   controlled output in y (B x n_outputs), as cmpc_produce_lin's; band (host,
+ *   S*ny, or NULL for 0) the settling bands; Ts the sampling time.  Allocates
+ *   the context's own record and resets it.  Refused: out_idx outside
+ *   [0, n_outputs), a negative or non-finite band or Ts, dimensions without a
+ *   kernel instance.  cmpc_score_check is the same check without a context
+ *   (host only).  A context that never enables scoring allocates and launches
+ *   nothing for it.
+ * cmpc_score_bind: keep the record in a caller's device buffer (len*B*S
+ *   doubles, checked as cmpc_bind_state checks its pointers, 8-byte aligned);
+ *   NULL: the context's own again.  The buffer is taken as it is: follow with
+ *   cmpc_score_reset.
+ * cmpc_score_capture: also record the trajectories of n_sel chosen scenarios
+ *   (host list), one row [y (n_outputs) | u_control (nu_tot) | x (ns)] per
+ *   step k < t_cap into a t_cap x n_sel x width buffer, in the same launch;
+ *   later steps are dropped, not wrapped.  n_sel = 0 turns it off.  Refused:
+ *   t_cap < 1, an index outside [0, B) or given twice
+ *   (cmpc_score_capture_check: the same, host only).  The buffer is allocated
+ *   here and zeroed; cmpc_score_bind_capture puts the rows into a caller's
+ *   device buffer instead (checked as above; NULL: the own one).
+ * cmpc_score_reset: every field to 0, last_out and plant_fail_step to -1,
+ *   k = 0, the context's own capture buffer to 0.
+ * cmpc_score_step: device pointers, asynchronous on the ctx stream.  y: B x
+ *   n_outputs; target: B*S x ny or NULL; plant_status: B int32 (the
+ *   simulator's status words) or NULL; u_control (B x nu_tot) and x (B x ns)
+ *   feed the capture only and may be NULL (their columns stay zero).  Valid
+ *   once a solve has run (cmpc_iterate, cmpc_step, any cmpc_control_step*,
+ *   cmpc_get_input, cmpc_init_warmstart); it scores that solve's results as
+ *   they stand in the context, so call it after the step's solves and before
+ *   the next build.  Refused: not enabled, NULL y, no solve yet.
+ * cmpc_score_download: len*B*S doubles of the record in force.
+ * cmpc_score_download_capture: the t_cap*n_sel*width rows and the number of
+ *   steps recorded, min(k, t_cap) (either pointer may be NULL).
+ * cmpc_score_disable: frees what enable and capture allocated; later score
+ *   calls are refused until the next enable. */
+int cmpc_score_len(const cmpc_dims* dims);
+int cmpc_score_field(const cmpc_dims* dims, const char* name, int* offset, int* count);
+int cmpc_score_check(const cmpc_dims* dims, int n_outputs, const int32_t* out_idx, double Ts, const double* band);
+int cmpc_score_capture_check(const cmpc_dims* dims, int n_sel, const int32_t* scenarios, int t_cap);
+int cmpc_score_enable(cmpc_ctx* ctx, int n_outputs, const int32_t* out_idx /* S*ny, host */, double Ts,
+                      const double* band /* S*ny, host, or NULL: 0 */);
+int cmpc_score_bind(cmpc_ctx* ctx, double* scores_device /* len*B*S, or NULL: own buffer */);
+int cmpc_score_capture(cmpc_ctx* ctx, int n_sel, const int32_t* scenarios /* host */, int t_cap);
+int cmpc_score_bind_capture(cmpc_ctx* ctx, double* rows_device /* t_cap*n_sel*width, or NULL: own buffer */);
+int cmpc_score_reset(cmpc_ctx* ctx);
+int cmpc_score_step(cmpc_ctx* ctx, const double* y, const double* target, const int32_t* plant_status,
+                    const double* u_control, const double* x);
+int cmpc_score_download(cmpc_ctx* ctx, double* scores);
+int cmpc_score_download_capture(cmpc_ctx* ctx, double* rows, int32_t* n_rows);
+int cmpc_score_disable(cmpc_ctx* ctx);
+
 /* Per-kernel device time (HIP events stamped by the kernel's own dispatch,
  * opt-in).  enable: 0 off, 1 every kernel, or an OR of CMPC_TIME_ONLY(k)
  * to time only those kernels (the others launch without events). */
