@@ -45,6 +45,28 @@
 #include "dispatch.h"
 #include "rows_blocks.inc"
 
+// How many steps ahead the horizon loop reads a step's zeroed P accumulators
+// from LDS (CMPC_PAIR_STEP).  Both forms are bit-identical; 1 measured faster
+// (DESIGN §3.2b).
+#ifndef CMPC_PAIR_ZDEPTH
+#define CMPC_PAIR_ZDEPTH 1
+#endif
+static_assert(CMPC_PAIR_ZDEPTH == 1 || CMPC_PAIR_ZDEPTH == 2, "CMPC_PAIR_ZDEPTH");
+
+// Wait for the staging DMA.  This is an S_WAITCNT instruction of the compiler's
+// own (vmcnt(0), the other counters left alone), not inline assembly: a
+// global_load_lds counts on vmcnt and on lgkmcnt, so the wait-count pass keeps
+// it as a pending "flat" access until it has seen a wait on BOTH counters, and
+// while one is pending it turns every counted lgkmcnt(N) into lgkmcnt(0).  It
+// cannot read a wait inside an asm string: with `asm("s_waitcnt vmcnt(0)")`
+// the DMA of pass 1's restaging stayed pending round the pass loop's back
+// edge, and every horizon step drained the LDS queue before its first FMA.
+__device__ __forceinline__ void pair_wait_dma() {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // gfx9 encoding: vmcnt 0, expcnt 7, lgkmcnt 15
+  asm volatile("" ::: "memory");
+}
+
 template <int NS, int NY, int NUT, int NU, int M, int ND>
 __global__ __launch_bounds__(64 * CMPC_BUILD_WAVES) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void cmpc_build_pair_kernel(BuildParams P) {
@@ -246,7 +268,7 @@ void cmpc_build_pair_kernel(BuildParams P) {
 #pragma unroll
         for (int o2 = 0; o2 < NY; ++o2) dyr[s][o2] = P.dy_ref[qo + s * NY + o2];
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    pair_wait_dma();
     uint64_t diff = 0ull;
 #pragma unroll
     for (int sc = 0; sc < 4; ++sc) {
@@ -407,14 +429,19 @@ void cmpc_build_pair_kernel(BuildParams P) {
 
 // one horizon step (build_rows_kernel.h, its PIPE and ZL forms): the first
 // link groups of the five chains, the gather columns' running sums, then the
-// other link groups with the 24 gather FMAs spread between them
+// other link groups with the 24 gather FMAs spread between them.
+// z1 / z2: the zeroed P accumulators of the coming steps, read from LDS
+// CMPC_PAIR_ZDEPTH steps before they are consumed.  1: a step reads the next
+// step's set at its end and the head waits for those reads alone
+// (lgkmcnt(8): the step's own hand-off traffic stays in flight).  2: it reads
+// the set of step u + 2, and no step's first FMA waits on an LDS read.
 #define CMPC_PAIR_STEP(u)                                                                  \
   {                                                                                        \
     double aS0 = aN0, aS1 = aN1;                                                           \
     yh0 = yp0[u];                                                                          \
     yh1 = yp1[u];                                                                          \
     double aP[NY];                                                                         \
-    _Pragma("unroll") for (int o = 0; o < NY; ++o) aP[o] = zn[o];                          \
+    _Pragma("unroll") for (int o = 0; o < NY; ++o) aP[o] = z1[o];                          \
     rows_pair_head<NS, NY, ND, NUT, M>(pP, pS0, pS1, mP, mS, aP, aS0, aS1, cv, acc);       \
     __builtin_amdgcn_sched_barrier(0);                                                     \
     _Pragma("unroll") for (int o = 0; o < NY; ++o) cv[o] = __builtin_fma(smask, cv[o], rd[o]); \
@@ -425,7 +452,12 @@ void cmpc_build_pair_kernel(BuildParams P) {
     _Pragma("unroll") for (int o = 0; o < NY; ++o) pP[o] = aP[o];                          \
     pS0 = aS0;                                                                             \
     pS1 = aS1;                                                                             \
-    _Pragma("unroll") for (int o = 0; o < NY; ++o) zn[o] = zeros[o];                       \
+    if constexpr (CMPC_PAIR_ZDEPTH == 2) {                                                 \
+      _Pragma("unroll") for (int o = 0; o < NY; ++o) z1[o] = z2[o];                        \
+      _Pragma("unroll") for (int o = 0; o < NY; ++o) z2[o] = zeros[o];                     \
+    } else {                                                                               \
+      _Pragma("unroll") for (int o = 0; o < NY; ++o) z1[o] = zeros[o];                     \
+    }                                                                                      \
     _Pragma("unroll") for (int o = 0; o < NY; ++o) wq[(u) * NY + o] = aP[o];               \
     zq0[(u) * NY] = aS0;                                                                   \
     zq1[(u) * NY] = aS1;                                                                   \
@@ -441,9 +473,9 @@ void cmpc_build_pair_kernel(BuildParams P) {
 
       int r = 0;
       double aN0 = base0 + yh0, aN1 = base1 + yh1;  // start values of the next step's free responses
-      double zn[NY];                                // the next step's zeroed P accumulators (from LDS)
+      double z1[NY], z2[NY];                        // zeroed P accumulators of the coming steps (from LDS)
 #pragma unroll
-      for (int o = 0; o < NY; ++o) zn[o] = zeros[o];
+      for (int o = 0; o < NY; ++o) z1[o] = z2[o] = zeros[o];
       for (int sg = 0; sg <= nseg; ++sg) {
         int r_end = pp;
 #pragma unroll
@@ -527,7 +559,7 @@ void cmpc_build_pair_kernel(BuildParams P) {
       // pass 1: slot 1's records whole, slot 0's tails
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       stage(1);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      pair_wait_dma();
     }
   }
   if (lane == 0 && shared_scn) atomicAdd(P.pair_cnt, shared_scn);
