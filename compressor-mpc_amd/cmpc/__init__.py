@@ -35,7 +35,8 @@ __all__ = ["Context", "ControllerConfig", "SetupFile", "reference_config", "refe
            "CMPC_QP_MAX_NWSR", "CMPC_QP_INFEASIBLE", "CMPC_QP_NOT_PD",
            "CMPC_QP_NONFINITE", "build_pairing_available", "build_pairing_reason", "CMPC_PAIRING_AUTO",
            "CMPC_PAIRING_OFF", "CMPC_PAIRING_ON", "scenario_weights_available", "weight_factor",
-           "CMPC_PLAN_SCENARIO_WEIGHTS", "score_len", "score_fields", "score_check", "score_capture_check"]
+           "CMPC_PLAN_SCENARIO_WEIGHTS", "score_len", "score_fields", "score_check", "score_capture_check",
+           "certify_len", "certify_fields", "certify_available"]
 
 
 def layout_of(dims: CmpcDims) -> CmpcLayout:
@@ -122,6 +123,32 @@ def score_capture_check(dims: CmpcDims, scenarios, t_cap: int) -> np.ndarray:
     check(load_library().cmpc_score_capture_check(ctypes.byref(dims), int(sel.size), iptr(sel), int(t_cap)),
           "cmpc_score_capture_check")
     return sel
+
+
+def certify_len(dims: CmpcDims) -> int:
+    """Rows of a QP slot's certificate record, 2 nV + 9 (cmpc_certify_len, host only)."""
+    n = load_library().cmpc_certify_len(ctypes.byref(dims))
+    check(min(n, 0), "cmpc_certify_len")
+    return n
+
+
+def certify_fields(dims: CmpcDims) -> dict:
+    """{field name: slice of the record's rows} for dims, from the library's
+    own table (cmpc_certify_field, host only).  The record is field-major: a
+    download reshaped to (certify_len, B*S) is indexed by these slices."""
+    lib = load_library()
+    out = {}
+    for name in _abi.CERTIFY_FIELDS:
+        off, cnt = ctypes.c_int(), ctypes.c_int()
+        check(lib.cmpc_certify_field(ctypes.byref(dims), name.encode(), ctypes.byref(off), ctypes.byref(cnt)),
+              "cmpc_certify_field")
+        out[name] = slice(off.value, off.value + cnt.value)
+    return out
+
+
+def certify_available(dims: CmpcDims) -> bool:
+    """Whether Context.certify has a kernel instance for dims (host only)."""
+    return bool(load_library().cmpc_certify_available(ctypes.byref(dims)))
 
 
 def predict_available(dims: CmpcDims) -> bool:
@@ -705,6 +732,49 @@ class Context:
         """Device addresses of (y_pred, cost); (0, 0) before the first predict."""
         return (self.lib.cmpc_prediction_device(self._h) or 0,
                 self.lib.cmpc_prediction_cost_device(self._h) or 0)
+
+    # -- multipliers and KKT certificate (include/cmpc.h, cmpc_certify*) ----
+    def certify(self, du_other_ptr: int = 0):
+        """Lagrange multipliers and KKT residuals of every QP slot for the
+        context's current plans and the other controllers' plans at
+        du_other_ptr (device, (B*S, nVo) in predict's order; 0: gathered from
+        the scenario's other slots).  Refused unless a solve has written plans
+        for the last build and nothing they depend on has changed since.
+        Asynchronous; results through certify_download / certify_summary."""
+        check(self.lib.cmpc_certify(self._h, ctypes.c_void_p(du_other_ptr or None), 0), "cmpc_certify")
+
+    def certify_host(self, du_other=None):
+        """certify with the other controllers' plans in a host array (B*S, nVo) or None."""
+        d = None if du_other is None else np.ascontiguousarray(du_other, dtype=np.float64)
+        check(self.lib.cmpc_certify_host(self._h, dptr(d) if d is not None and d.size else None, 0),
+              "cmpc_certify_host")
+
+    def certify_ptr(self) -> int:
+        """Device address of the record; 0 before the first certify."""
+        return self.lib.cmpc_certify_device(self._h) or 0
+
+    def certify_record(self) -> np.ndarray:
+        """(certify_len, B*S): the last record as stored, field-major."""
+        out = np.zeros((certify_len(self.dims), self.nqp))
+        check(self.lib.cmpc_certify_download(self._h, dptr(out)), "cmpc_certify_download")
+        return out
+
+    def certify_download(self) -> dict:
+        """The last record by field name: lam (B*S, 2 nV), every other field (B*S,)."""
+        rec = self.certify_record()
+        out = {}
+        for name, sl in certify_fields(self.dims).items():
+            out[name] = np.ascontiguousarray(rec[sl].T) if name == "lam" else rec[sl.start].copy()
+        return out
+
+    def certify_summary(self, tol: float = 1e-9) -> dict:
+        """The device's reduction of the last record over the OK slots
+        (cmpc_certify_summary): the largest r_stat/scale, r_prim, r_dual/scale,
+        r_comp/scale with their slots, n_above (OK slots with any of the four
+        above tol) and n_not_ok."""
+        out = _abi.CmpcCertifySummary()
+        check(self.lib.cmpc_certify_summary(self._h, float(tol), ctypes.byref(out)), "cmpc_certify_summary")
+        return out.as_dict()
 
     # -- closed-loop performance indices (include/cmpc.h, cmpc_score_*) -----
     def score_fields(self) -> dict:

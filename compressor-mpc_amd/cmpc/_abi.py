@@ -157,12 +157,28 @@ EXPORTS = (
     "cmpc_score_enable", "cmpc_score_bind", "cmpc_score_capture", "cmpc_score_bind_capture",
     "cmpc_score_reset", "cmpc_score_step", "cmpc_score_download", "cmpc_score_download_capture",
     "cmpc_score_disable",
+    "cmpc_certify_len", "cmpc_certify_field", "cmpc_certify_available", "cmpc_certify", "cmpc_certify_host",
+    "cmpc_certify_device", "cmpc_certify_download", "cmpc_certify_summary",
 )
 
 # the fields of a slot's score record, in the record's order (cmpc_score_field
 # gives each one's rows; include/cmpc.h has the table)
 SCORE_FIELDS = ("n", "ise", "iae", "peak", "last_out", "j_track", "j_move", "tv", "sat_bound", "sat_rate",
                 "n_fail", "nwsr_sum", "plant_fail_step")
+
+# the fields of a slot's certificate record, in the record's order
+# (cmpc_certify_field gives each one's rows; include/cmpc.h has the table)
+CERTIFY_FIELDS = ("lam", "r_stat", "r_prim", "r_dual", "r_comp", "obj", "scale", "n_active", "status", "rank_def")
+
+
+class CmpcCertifySummary(ctypes.Structure):
+    """cmpc_certify_summary_t (include/cmpc.h)."""
+    _fields_ = ([(n, ctypes.c_double) for n in ("r_stat", "r_prim", "r_dual", "r_comp")] +
+                [(n, ctypes.c_int32) for n in ("slot_stat", "slot_prim", "slot_dual", "slot_comp",
+                                               "n_above", "n_not_ok")])
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 _lib = None
 
@@ -327,6 +343,14 @@ def load_library(path: str = LIB_PATH):
         "cmpc_score_download": ([c_void, P(dbl)], ctypes.c_int),
         "cmpc_score_download_capture": ([c_void, P(dbl), P(i32)], ctypes.c_int),
         "cmpc_score_disable": ([c_void], ctypes.c_int),
+        "cmpc_certify_len": ([P(CmpcDims)], ctypes.c_int),
+        "cmpc_certify_field": ([P(CmpcDims), ctypes.c_char_p, P(ctypes.c_int), P(ctypes.c_int)], ctypes.c_int),
+        "cmpc_certify_available": ([P(CmpcDims)], ctypes.c_int),
+        "cmpc_certify": ([c_void, c_void, u32], ctypes.c_int),
+        "cmpc_certify_host": ([c_void, P(dbl), u32], ctypes.c_int),
+        "cmpc_certify_device": ([c_void], c_void),
+        "cmpc_certify_download": ([c_void, P(dbl)], ctypes.c_int),
+        "cmpc_certify_summary": ([c_void, dbl, P(CmpcCertifySummary)], ctypes.c_int),
         "cmpc_qp_solve_batch": ([ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(dbl),
                                  P(dbl), P(dbl), P(dbl), P(dbl), P(dbl), P(u32), ctypes.c_int,
                                  P(dbl), P(i32), P(i32), P(u32), P(ctypes.c_uint8), P(i32)],

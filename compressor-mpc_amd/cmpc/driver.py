@@ -392,7 +392,7 @@ class ClosedLoop:
         if self._scores:
             self.ctx.score_reset()
 
-    def step(self, trace: bool = False, predict: bool = False):
+    def step(self, trace: bool = False, predict: bool = False, certify=None):
         """One sampling instant: returns (t, y) of the instant; the plant has
         advanced to the next one.  trace: the Jacobi iterations record their
         working-set changes (CMPC_TRACE); self.last_changes is then their
@@ -400,7 +400,12 @@ class ClosedLoop:
         predict: the instant's plans are evaluated against the model they were
         computed from (Context.predict, before the move is applied);
         self.last_prediction (B*S, p, ny) and self.last_cost (B*S, 2) are then
-        host arrays.  The step itself computes the same with or without."""
+        host arrays.  certify: at the same point the instant's multipliers and
+        KKT residuals are computed (Context.certify, the other controllers'
+        plans gathered from the final ones: r_stat is the Jacobi gap) and
+        self.last_certificate is their summary (Context.certify_summary) at
+        tolerance `certify` (True: 1e-9).  The step itself computes the same
+        with or without either."""
         from ._abi import check, iptr
         t = 0.0 + self.k * self.Ts   # the record's label (record count)
         # integrate_const's own time: start_time + step * dt of the current
@@ -422,6 +427,9 @@ class ClosedLoop:
         if predict:
             self.ctx.predict()
             self.last_prediction, self.last_cost = self.ctx.download_prediction()
+        if certify is not None and certify is not False:
+            self.ctx.certify()
+            self.last_certificate = self.ctx.certify_summary(1e-9 if certify is True else float(certify))
         self.ctx.observe_apply()
         check(self.ctx.lib.cmpc_accumulate_moves(self.ctx._h, iptr(self.io),
                                                  self.torch_ptr(self.u_ctrl)), "cmpc_accumulate_moves")

@@ -220,6 +220,13 @@ struct cmpc_ctx {
   bool pred_done = false;
   bool pred_built = false;  // a build has run
   const char* pred_stale = nullptr;
+  // multipliers and KKT certificate (cmpc_certify): the record and the
+  // summary's work buffer are allocated by the first call; cert_plans: a solve
+  // has written plans for the last build's QPs
+  double* cert_rec = nullptr;
+  void* cert_work = nullptr;
+  bool cert_done = false;
+  bool cert_plans = false;
   // closed-loop performance indices (cmpc_score_*): everything is allocated by
   // cmpc_score_enable / cmpc_score_capture and freed by cmpc_score_disable;
   // score_rec / score_cap are the buffers in force (own or bound)
@@ -569,7 +576,7 @@ int cmpc_destroy(cmpc_ctx* c) {
                   c->own_ws ? c->own_ws : c->ws,
                   c->trace, c->ntrace, c->obs, c->d_obsM,
                   c->stage, c->own_sc_dy, c->own_sc_limits, c->own_sc_dref, c->own_sc_w, c->own_sc_p, c->d_yref, c->pred_y,
-                  c->pred_cost,
+                  c->pred_cost, c->cert_rec, c->cert_work,
                   c->pair_cnt, c->score_band, c->score_oi, c->score_own, c->score_map, c->score_cap_own};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -1377,6 +1384,7 @@ static int control_step(cmpc_ctx* c, const double* u_full, const double* y, int 
   c->last_solve = pl.control_solve_kernel;
   c->last_step_fused = 1;
   c->pred_built = true;  // (and stale at once: the a-priori phase has moved u_old)
+  c->cert_plans = K > 0;
   c->obs_steps++;  // the delay-block rings advance by one (cmpc_observe_apply)
   if (flagged) *flagged = flag;
   return tl.end();
@@ -2073,6 +2081,7 @@ int cmpc_build(cmpc_ctx* c) {
   }
   c->pred_built = true;
   c->pred_stale = nullptr;
+  c->cert_plans = false;
   return 0;
 }
 
@@ -2161,6 +2170,7 @@ int cmpc_iterate(cmpc_ctx* c, int K, uint32_t flags) {
   if (flags & CMPC_APPLY_MOVE) c->pred_stale = kStaleMove;
   if (launch_solve(c, P, kernel)) return -1;
   if (check_launch("iterate kernel")) return -1;
+  if (K > 0) c->cert_plans = true;
   return tl.end();
 }
 
@@ -2185,6 +2195,7 @@ int cmpc_get_input(cmpc_ctx* c, const double* du_last, uint32_t flags) {
   if (flags & CMPC_APPLY_MOVE) c->pred_stale = kStaleMove;
   if (launch_solve(c, P, kernel)) return -1;
   if (check_launch("get-input kernel")) return -1;
+  c->cert_plans = true;
   return tl.end();
 }
 
@@ -2352,6 +2363,7 @@ int cmpc_step(cmpc_ctx* c, int K, uint32_t flags) {
   c->last_step_fused = 1;
   c->pred_built = true;
   c->pred_stale = (flags & CMPC_APPLY_MOVE) ? kStaleMove : nullptr;
+  c->cert_plans = K > 0;
   return tl.end();
 }
 
@@ -2500,6 +2512,126 @@ int cmpc_download_prediction(cmpc_ctx* c, double* y_pred, double* cost) {
                            c->stream));
   if (cost) HIP_TRY(hipMemcpyAsync(cost, c->pred_cost, sizeof(double) * n * 2, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// Multipliers and KKT certificate of every QP slot (include/cmpc.h, certify.hip).
+static const struct {
+  const char* name;
+  int CertifyFields::*row;
+} kCertifyFields[] = {
+    {"lam", &CertifyFields::lam},           {"r_stat", &CertifyFields::r_stat},
+    {"r_prim", &CertifyFields::r_prim},     {"r_dual", &CertifyFields::r_dual},
+    {"r_comp", &CertifyFields::r_comp},     {"obj", &CertifyFields::obj},
+    {"scale", &CertifyFields::scale},       {"n_active", &CertifyFields::n_active},
+    {"status", &CertifyFields::status},     {"rank_def", &CertifyFields::rank_def},
+};
+
+int cmpc_certify_len(const cmpc_dims* dims) {
+  cmpc_layout L;
+  if (!dims) return fail("null argument");
+  if (layout_of(dims, &L)) return -1;
+  return cmpc_certify_fields(L.nV).len;
+}
+
+int cmpc_certify_field(const cmpc_dims* dims, const char* name, int* offset, int* count) {
+  cmpc_layout L;
+  if (!dims || !name) return fail("null argument");
+  if (layout_of(dims, &L)) return -1;
+  const CertifyFields F = cmpc_certify_fields(L.nV);
+  for (const auto& f : kCertifyFields)
+    if (!std::strcmp(name, f.name)) {
+      if (offset) *offset = F.*(f.row);
+      if (count) *count = f.row == &CertifyFields::lam ? 2 * L.nV : 1;
+      return 0;
+    }
+  return fail(std::string("cmpc_certify_field: no field named '") + name + "'");
+}
+
+int cmpc_certify_available(const cmpc_dims* dims) {
+  cmpc_layout L;
+  if (!dims || cmpc_layout_error(dims, &L) || cmpc_context_dims_error(*dims, L)) return 0;
+  return cmpc_certify_instance(L.nV, dims->nu, L.nVo) ? 1 : 0;
+}
+
+int cmpc_certify(cmpc_ctx* c, const double* du_other, uint32_t flags) {
+  if (!c) return fail("null context");
+  if (flags) return fail("cmpc_certify: flags must be 0 (reserved)");
+  if (!cmpc_certify_instance(c->L.nV, c->d.nu, c->L.nVo))
+    return fail("cmpc_certify: certify kernel not instantiated for these dimensions (nV, nu, nVo)");
+  if (!c->pred_built) return fail("cmpc_certify: no build has run (cmpc_build, cmpc_step or cmpc_control_step)");
+  if (c->pred_stale) return fail(std::string("cmpc_certify: ") + c->pred_stale);
+  if (!c->cert_plans)
+    return fail("cmpc_certify: no solve has written plans for the last build (cmpc_iterate or cmpc_step with "
+                "K > 0, cmpc_get_input)");
+  if (c->L.nVo == 0) du_other = nullptr;
+  if (c->L.nVo > 0 && !du_other && c->d.nu_tot != c->d.S * c->d.nu)
+    return fail("cmpc_certify: the other controllers' plans are not in this context (nu_tot != S * nu): "
+                "give du_other");
+  if (ensure_cfg(c)) return -1;
+  HIP_TRY(hipSetDevice(c->device));
+  const CertifyFields F = cmpc_certify_fields(c->L.nV);
+  if (!c->cert_rec) HIP_TRY(hipMalloc(&c->cert_rec, sizeof(double) * (size_t)F.len * c->nqp));
+  if (!c->cert_work) HIP_TRY(hipMalloc(&c->cert_work, cmpc_certify_summary_bytes()));
+  CertifyParams P;
+  std::memset(&P, 0, sizeof P);
+  P.rec = c->cert_rec;
+  P.qp = c->qp;
+  P.cfg = c->cfg;
+  P.limits = c->sc_limits;
+  P.u_old = c->u_old;
+  P.du = c->du;  // (page-locked host memory up to CMPC_HOST_OUT_MAX_QP slots: its device address)
+  P.d = du_other;
+  P.ws = c->ws;
+  P.status = c->status;
+  P.nqp = c->nqp;
+  P.S = c->d.S;
+  P.nu_tot = c->d.nu_tot;
+  P.qp_len = c->qp_len;
+  P.co = c->co;
+  if (cmpc_launch_certify(P, c->L.nV, c->d.nu, c->L.nVo, c->stream)) return plan_mismatch("certify");
+  if (check_launch("certify kernel")) return -1;
+  c->cert_done = true;
+  return 0;
+}
+
+int cmpc_certify_host(cmpc_ctx* c, const double* du_other, uint32_t flags) {
+  if (!c) return fail("null context");
+  if (!du_other || !c->L.nVo) return cmpc_certify(c, nullptr, flags);
+  HIP_TRY(hipSetDevice(c->device));
+  const double* h[1] = {du_other};
+  const size_t n[1] = {(size_t)c->nqp * c->L.nVo};
+  const double* d[1];
+  if (stage_host(c, h, n, 1, d)) return -1;
+  const int rc = cmpc_certify(c, d[0], flags);
+  return stage_done(c) ? -1 : rc;
+}
+
+double* cmpc_certify_device(cmpc_ctx* c) { return c && c->cert_done ? c->cert_rec : nullptr; }
+
+int cmpc_certify_download(cmpc_ctx* c, double* record) {
+  if (!c || !record) return fail("null argument");
+  if (!c->cert_done) return fail("cmpc_certify_download: nothing has been certified (cmpc_certify)");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemcpyAsync(record, c->cert_rec,
+                         sizeof(double) * (size_t)cmpc_certify_fields(c->L.nV).len * c->nqp,
+                         hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int cmpc_certify_summary(cmpc_ctx* c, double tol, cmpc_certify_summary_t* out) {
+  if (!c || !out) return fail("null argument");
+  if (!c->cert_done) return fail("cmpc_certify_summary: nothing has been certified (cmpc_certify)");
+  if (!(tol >= 0)) return fail("cmpc_certify_summary: tol must be >= 0");
+  HIP_TRY(hipSetDevice(c->device));
+  if (cmpc_launch_certify_summary(c->cert_rec, c->nqp, c->L.nV, tol, c->cert_work, c->stream))
+    return plan_mismatch("certify summary");
+  if (check_launch("certify summary kernels")) return -1;
+  alignas(8) unsigned char head[kCertifySummaryHead];
+  HIP_TRY(hipMemcpyAsync(head, c->cert_work, sizeof head, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  cmpc_certify_summary_unpack(head, out);
   return 0;
 }
 

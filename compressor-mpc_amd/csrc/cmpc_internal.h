@@ -328,6 +328,54 @@ int cmpc_launch_score(const ScoreParams& P, int ny, int nu, void* stream);
 // every field of every slot to 0, last_out and plant_fail_step to -1
 int cmpc_launch_score_reset(double* rec, int nqp, int ny, int nu, void* stream);
 
+// Multipliers and KKT certificate (certify.hip, cmpc_certify*, DESIGN.md
+// §3.16): one record per QP slot, field-major (row r of slot q at
+// r * nqp + q), all doubles.  The rows of each field, in the record's order;
+// the kernels, the host functions and cmpc_certify_field take them from here.
+struct CertifyFields {
+  int lam, r_stat, r_prim, r_dual, r_comp, obj, scale, n_active, status, rank_def, len;
+};
+__host__ __device__ constexpr CertifyFields cmpc_certify_fields(int nV) {
+  CertifyFields F{};
+  int o = 0;
+  F.lam = o; o += 2 * nV;
+  F.r_stat = o; o += 1;
+  F.r_prim = o; o += 1;
+  F.r_dual = o; o += 1;
+  F.r_comp = o; o += 1;
+  F.obj = o; o += 1;
+  F.scale = o; o += 1;
+  F.n_active = o; o += 1;
+  F.status = o; o += 1;
+  F.rank_def = o; o += 1;
+  F.len = o;
+  return F;
+}
+struct CertifyParams {
+  double* rec;             // len * nqp records, field-major
+  const double* qp;        // nqp * qp_len   [H nV*nV | f nV | G nV*nVo]
+  const double* cfg;       // S * co.len
+  const double* limits;    // nqp * 4 nu per-slot limits (SolveParams::limits), or null: the cfg block's
+  const double* u_old;     // nqp * nu_tot
+  const double* du;        // nqp * nV plans
+  const double* d;         // nqp * nVo other controllers' plans (cmpc_predict's order), or null:
+                           // gathered from du of the scenario's other slots
+  const uint32_t* ws;      // nqp working-set words of the state in force
+  const int32_t* status;   // nqp
+  int nqp, S, nu_tot, qp_len;
+  CfgOffsets co;
+};
+bool cmpc_certify_instance(int nV, int nu, int nVo);
+// one lane per QP slot, 64-lane workgroups; -1: no instance for (nV, nu, nVo)
+int cmpc_launch_certify(const CertifyParams& P, int nV, int nu, int nVo, void* stream);
+// The summary: two launches over the record's residual rows; `work` holds
+// cmpc_certify_summary_bytes() bytes, its head the result once both have run
+// (cmpc_certify_summary_unpack turns a host copy of the head into the ABI's struct).
+size_t cmpc_certify_summary_bytes();
+int cmpc_launch_certify_summary(const double* rec, int nqp, int nV, double tol, void* work, void* stream);
+void cmpc_certify_summary_unpack(const void* work_head, cmpc_certify_summary_t* out);
+constexpr size_t kCertifySummaryHead = 64;  // bytes of the head (>= the partial's size)
+
 // Standalone batched solver (parity / KKT tests).  G (nqp * n * nvo) and d
 // (nqp * nvo) non-null: the Jacobi iteration's map-form solve with g = f + G d
 // (cmpc_qp_solve_batch_map); g is f then.

@@ -644,6 +644,88 @@ int cmpc_score_download(cmpc_ctx* ctx, double* scores);
 int cmpc_score_download_capture(cmpc_ctx* ctx, double* rows, int32_t* n_rows);
 int cmpc_score_disable(cmpc_ctx* ctx);
 
+/* Lagrange multipliers and a KKT certificate per QP slot (certify.hip,
+ * DESIGN.md §3.16): qpOASES's getDualSolution for the library's own solver,
+ * and evidence on the device that a slot's "OK" is an optimum.
+ *
+ * For QP slot q = b*S + s, n = nV: x the slot's plan (what cmpc_download
+ * returns as du); H, f, G of the last build (f corrected where a reference
+ * profile is in force); d (nVo) the other controllers' plans in cmpc_predict's
+ * order d[mv*nuo + rank*nu + c].  The 2n constraint rows are C = [I; A], A = I
+ * with A[i][i-nu] = -1 for i >= nu, with the solver's limits (c = j mod nu):
+ *   lo[j]   = lower[c] - u_old[q][c],  hi[j]   = upper[c] - u_old[q][c]   j < n
+ *   lo[n+j] = rate_lower[c],           hi[n+j] = rate_upper[c]
+ * (the slot's own limits where cmpc_set/bind_scenario_constraints is in
+ * force).  The working set W is the slot's working-set word in the state in
+ * force (bound state included): bit j, row j is active; bit 16+j, on its upper
+ * side.  W is taken as empty where status != CMPC_QP_OK (such slots hold the
+ * zero move).  With g = H x + f + G d, cx = C x and t[j] the active side's
+ * limit, the record of a slot is
+ *
+ *   field      rows  value
+ *   lam        2n    on W the least-squares solution of C_W' lam_W = g, 0 off
+ *                    W; qpOASES's sign: >= 0 on an active lower side, <= 0 on
+ *                    an active upper side.  Rows 0..n-1 the bounds, n..2n-1
+ *                    the rate rows
+ *   r_stat     1     max_i |g - C' lam|_i
+ *   r_prim     1     max_j max(lo[j] - cx[j], cx[j] - hi[j], 0), all 2n rows
+ *   r_dual     1     the largest wrong-signed |lam[j]| over W; 0 if none
+ *   r_comp     1     max over W of |lam[j]| |cx[j] - t[j]|
+ *   obj        1     1/2 x'Hx + (f + G d)'x
+ *   scale      1     max|H| max(1, max|x|) + max_i |f + G d|_i + 1
+ *   n_active   1     rows in W
+ *   status     1     the slot's status word
+ *   rank_def   1     1 where the normals of W are dependent (the solver's own
+ *                    dependency test should exclude it for an OK slot): lam = 0
+ *
+ * All rows are doubles, in this order, cmpc_certify_len(dims) = 2 nV + 9 rows.
+ * Storage is field-major: row r of slot q at r*B*S + q.  cmpc_certify_field
+ * gives a field's first row and row count by name (-1 for an unknown name);
+ * callers take offsets from it.
+ *
+ * Two readings.  With d what the slot's last solve saw (nVo = 0; the du_last
+ * of cmpc_get_input; after cmpc_iterate(1) the du_old in force before it), an
+ * OK slot's residuals certify the solver: all four are rounding-sized against
+ * scale.  With d NULL after K iterations, d is gathered from the scenario's
+ * other slots' final plans and r_stat is the scenario's Jacobi gap: zero
+ * exactly at a fixed point of the iteration.
+ *
+ * cmpc_certify: asynchronous on the ctx stream; du_other_device NULL gathers
+ *   d as cmpc_predict does (needs nu_tot = S * nu); ignored for nVo = 0.
+ *   flags must be 0.  It changes nothing the solve wrote.  Refused (-1, the
+ *   message names the cause): dimensions without an instance, before a build,
+ *   before a solve has written plans for that build (cmpc_iterate with K > 0,
+ *   cmpc_step with K > 0, cmpc_get_input), and after any call on the list that
+ *   invalidates cmpc_predict (above): lo and hi depend on u_old.
+ * cmpc_certify_host: d from host memory (staged as the other _host calls).
+ * cmpc_certify_device: the record's device address; NULL before the first
+ *   cmpc_certify, which allocates it: a context that never certifies allocates
+ *   and launches nothing for it.
+ * cmpc_certify_download: len*B*S doubles of the last record.
+ * cmpc_certify_summary: a small two-pass reduction on the device over the
+ *   slots with status == CMPC_QP_OK: the largest r_stat/scale, r_prim,
+ *   r_dual/scale and r_comp/scale, each with its slot (the lowest on ties; 0
+ *   and -1 without an OK slot), n_above the OK slots with any of the four
+ *   above tol, n_not_ok the other slots.  Maxima and counts are exact in any
+ *   order: the result equals the same reduction of the downloaded record bit
+ *   for bit.  Synchronises the stream.
+ * cmpc_certify_available: host only, 1 where an instance exists (every
+ *   (nV, nu, nVo) the iterate kernels are instantiated for), 0 elsewhere.
+ * cmpc_certify_len, cmpc_certify_field: host only. */
+typedef struct cmpc_certify_summary_t {
+  double r_stat, r_prim, r_dual, r_comp;
+  int32_t slot_stat, slot_prim, slot_dual, slot_comp;
+  int32_t n_above, n_not_ok;
+} cmpc_certify_summary_t;
+int cmpc_certify_len(const cmpc_dims* dims);
+int cmpc_certify_field(const cmpc_dims* dims, const char* name, int* offset, int* count);
+int cmpc_certify_available(const cmpc_dims* dims);
+int cmpc_certify(cmpc_ctx* ctx, const double* du_other_device, uint32_t flags);
+int cmpc_certify_host(cmpc_ctx* ctx, const double* du_other, uint32_t flags);
+double* cmpc_certify_device(cmpc_ctx* ctx);
+int cmpc_certify_download(cmpc_ctx* ctx, double* record);
+int cmpc_certify_summary(cmpc_ctx* ctx, double tol, cmpc_certify_summary_t* out);
+
 /* Per-kernel device time (HIP events stamped by the kernel's own dispatch,
  * opt-in).  enable: 0 off, 1 every kernel, or an OR of CMPC_TIME_ONLY(k)
  * to time only those kernels (the others launch without events). */
