@@ -22,7 +22,8 @@ from ._abi import (CMPC_BUILD_AUTO, CMPC_BUILD_ROWS, CMPC_BUILD_SPLIT, CMPC_BUIL
                    CMPC_APPLY_MOVE, CMPC_KERNEL_BUILD, CMPC_KERNEL_ITERATE,
                    CMPC_KERNEL_PRODUCE, CMPC_KERNEL_OBSERVE_POST, CMPC_KERNEL_OBSERVE_PRIOR, CMPC_QP_INFEASIBLE,
                    CMPC_QP_MAX_NWSR, CMPC_QP_NOT_PD, CMPC_QP_NONFINITE, CMPC_QP_OK, CMPC_TRACE, CmpcDims,
-                   CmpcLayout, CmpcPlan, CMPC_PLAN_DU_OTHER, CMPC_PLAN_REF_PROFILE, CMPC_PLAN_SCENARIO_WEIGHTS, bptr,
+                   CmpcLayout, CmpcNoiseKey, CmpcPlan, CMPC_NOISE_STREAM_INPUT, CMPC_NOISE_STREAM_MEASUREMENT,
+                   CMPC_PLAN_DU_OTHER, CMPC_PLAN_REF_PROFILE, CMPC_PLAN_SCENARIO_WEIGHTS, bptr,
                    check, dptr, iptr, load_library, uptr)
 from .configs import ControllerConfig, SetupFile, reference_config, reference_observer_gain, reference_setup
 from .problem import ControllerArrays, controller_arrays, plant_input_from_plans
@@ -36,7 +37,10 @@ __all__ = ["Context", "ControllerConfig", "SetupFile", "reference_config", "refe
            "CMPC_QP_NONFINITE", "build_pairing_available", "build_pairing_reason", "CMPC_PAIRING_AUTO",
            "CMPC_PAIRING_OFF", "CMPC_PAIRING_ON", "scenario_weights_available", "weight_factor",
            "CMPC_PLAN_SCENARIO_WEIGHTS", "score_len", "score_fields", "score_check", "score_capture_check",
-           "certify_len", "certify_fields", "certify_available"]
+           "certify_len", "certify_fields", "certify_available", "score_ensemble_unpack",
+           "noise_key", "noise_check", "noise_check_params", "noise_uniforms_host", "noise_step_host",
+           "noise_uniforms", "noise_step", "noise_uniforms_ptr", "noise_step_ptr",
+           "CMPC_NOISE_STREAM_MEASUREMENT", "CMPC_NOISE_STREAM_INPUT"]
 
 
 def layout_of(dims: CmpcDims) -> CmpcLayout:
@@ -123,6 +127,158 @@ def score_capture_check(dims: CmpcDims, scenarios, t_cap: int) -> np.ndarray:
     check(load_library().cmpc_score_capture_check(ctypes.byref(dims), int(sel.size), iptr(sel), int(t_cap)),
           "cmpc_score_capture_check")
     return sel
+
+
+def score_ensemble_unpack(dims: CmpcDims, flat) -> dict:
+    """cmpc_score_ensemble's len*S*6 doubles as {field: {stat: (S, rows) array}}
+    (host only): the layout is [row f][sub-controller s][stat], the stats in
+    _abi.ENSEMBLE_STATS' order; argmax and count come back as int64."""
+    n_stat = len(_abi.ENSEMBLE_STATS)
+    a = np.asarray(flat, dtype=np.float64)
+    if a.size != score_len(dims) * dims.S * n_stat:
+        raise ValueError(f"expected score_len * S * {n_stat} = {score_len(dims) * dims.S * n_stat} values, got {a.size}")
+    a = a.reshape(score_len(dims), dims.S, n_stat)
+    out = {}
+    for name, sl in score_fields(dims).items():
+        out[name] = {}
+        for k, stat in enumerate(_abi.ENSEMBLE_STATS):
+            v = np.ascontiguousarray(a[sl, :, k].T)
+            out[name][stat] = v.astype(np.int64) if stat in ("argmax", "count") else v
+    return out
+
+
+def noise_key(seed: int, stream: int = 0, scenario0: int = 0) -> CmpcNoiseKey:
+    """cmpc_noise_key of (seed, stream, first global scenario of the batch)."""
+    seed, stream, scenario0 = int(seed), int(stream), int(scenario0)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed must be inside [0, 2^64), got {seed}")
+    if not 0 <= stream < 2 ** 32 or not 0 <= scenario0 < 2 ** 32:
+        raise ValueError(f"stream and scenario0 must be inside [0, 2^32), got {stream} and {scenario0}")
+    return CmpcNoiseKey(seed, stream, scenario0)
+
+
+def _noise_step_arg(step: int) -> int:
+    step = int(step)
+    if not 0 <= step < 2 ** 64:
+        raise ValueError(f"step must be inside [0, 2^64), got {step}")
+    return step
+
+
+def noise_check(seed: int, step: int, B: int, n: int, stream: int = 0, scenario0: int = 0):
+    """The argument check of every noise entry point (cmpc_noise_check, host
+    only); raises with the library's message."""
+    key = noise_key(seed, stream, scenario0)
+    check(load_library().cmpc_noise_check(ctypes.byref(key), _noise_step_arg(step), int(B), int(n)),
+          "cmpc_noise_check")
+    return key
+
+
+def _noise_array(a, B: int, n: int, what: str):
+    """(n,) or (B, n) to a contiguous (B, n) float64 array; None stays None."""
+    if a is None:
+        return None
+    a = np.asarray(a, dtype=np.float64)
+    if a.shape not in ((n,), (B, n)):
+        raise ValueError(f"{what} must be (n = {n},) or (B = {B}, n), got {a.shape}")
+    return np.array(np.broadcast_to(a, (B, n)), order="C")
+
+
+def noise_check_params(B: int, n: int, sigma=None, rho=None):
+    """sigma finite and >= 0, rho inside [-1, 1] (cmpc_noise_check_params, host
+    only), each (n,) or (B, n) or None; returns them as (B, n) arrays."""
+    sg, rh = _noise_array(sigma, B, n, "sigma"), _noise_array(rho, B, n, "rho")
+    check(load_library().cmpc_noise_check_params(int(B), int(n), dptr(sg) if sg is not None else None,
+                                                 dptr(rh) if rh is not None else None), "cmpc_noise_check_params")
+    return sg, rh
+
+
+def noise_uniforms_host(seed: int, step: int, B: int, n: int, stream: int = 0, scenario0: int = 0) -> np.ndarray:
+    """(B, ceil(n/2), 2): the uniforms [u1, u2] of every Box-Muller pair
+    (cmpc_noise_uniforms_host, no device)."""
+    key = noise_check(seed, step, B, n, stream, scenario0)
+    u = np.zeros((B, (n + 1) // 2, 2))
+    check(load_library().cmpc_noise_uniforms_host(ctypes.byref(key), _noise_step_arg(step), int(B), int(n), dptr(u)),
+          "cmpc_noise_uniforms_host")
+    return u
+
+
+def noise_step_host(seed: int, step: int, B: int, n: int, sigma=None, rho=None, w=None, base=None,
+                    stream: int = 0, scenario0: int = 0) -> np.ndarray:
+    """(B, n): base + the step's disturbance on host arrays (cmpc_noise_step_host,
+    no device; include/cmpc.h has the arithmetic).  sigma, rho, base: (n,) or
+    (B, n) or None; w: the (B, n) contiguous float64 AR(1) state, updated in
+    place (needed with rho)."""
+    key = noise_check(seed, step, B, n, stream, scenario0)
+    sg, rh, bs = (_noise_array(a, B, n, what) for a, what in ((sigma, "sigma"), (rho, "rho"), (base, "base")))
+    if w is not None and (not isinstance(w, np.ndarray) or w.shape != (B, n) or w.dtype != np.float64
+                          or not w.flags["C_CONTIGUOUS"]):
+        raise ValueError(f"w must be a contiguous float64 array (B = {B}, n = {n})")
+    out = np.zeros((B, n))
+    opt = lambda a: dptr(a) if a is not None else None
+    check(load_library().cmpc_noise_step_host(ctypes.byref(key), _noise_step_arg(step), int(B), int(n), opt(sg),
+                                              opt(rh), opt(w), opt(bs), dptr(out)), "cmpc_noise_step_host")
+    return out
+
+
+def noise_uniforms_ptr(device: int, stream_ptr: int, key: CmpcNoiseKey, step: int, B: int, n: int, u_ptr: int):
+    """cmpc_noise_uniforms on raw device addresses (asynchronous on the stream)."""
+    check(load_library().cmpc_noise_uniforms(int(device), ctypes.c_void_p(stream_ptr or None), ctypes.byref(key),
+                                             _noise_step_arg(step), int(B), int(n), ctypes.c_void_p(u_ptr or None)),
+          "cmpc_noise_uniforms")
+
+
+def noise_step_ptr(device: int, stream_ptr: int, key: CmpcNoiseKey, step: int, B: int, n: int, sigma_ptr: int,
+                   rho_ptr: int, w_ptr: int, base_ptr: int, out_ptr: int):
+    """cmpc_noise_step on raw device addresses (0: NULL; asynchronous on the stream)."""
+    vp = lambda p: ctypes.c_void_p(p or None)
+    check(load_library().cmpc_noise_step(int(device), vp(stream_ptr), ctypes.byref(key), _noise_step_arg(step), int(B),
+                                         int(n), vp(sigma_ptr), vp(rho_ptr), vp(w_ptr), vp(base_ptr), vp(out_ptr)),
+          "cmpc_noise_step")
+
+
+def _noise_tensor(t, B: int, n: int, what: str, device=None):
+    import torch
+    if t is None:
+        return 0
+    if (not isinstance(t, torch.Tensor) or tuple(t.shape) != (B, n) or t.dtype != torch.float64 or not t.is_cuda
+            or not t.is_contiguous() or (device is not None and t.device != device)):
+        raise ValueError(f"{what} must be a contiguous float64 tensor (B = {B}, n = {n}) on the device of out")
+    return t.data_ptr()
+
+
+def noise_uniforms(seed: int, step: int, out, stream: int = 0, scenario0: int = 0):
+    """The uniforms of a step into `out`, a contiguous float64 device tensor
+    (B, ceil(n/2), 2), on torch's current stream (cmpc_noise_uniforms); n is
+    taken as 2 * out.shape[1].  Returns out."""
+    import torch
+    if (not isinstance(out, torch.Tensor) or out.dim() != 3 or out.shape[2] != 2 or out.dtype != torch.float64
+            or not out.is_cuda or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous float64 device tensor (B, ceil(n/2), 2)")
+    B, n = int(out.shape[0]), 2 * int(out.shape[1])
+    key = noise_check(seed, step, B, n, stream, scenario0)
+    noise_uniforms_ptr(out.device.index, torch.cuda.current_stream(out.device).cuda_stream, key, step, B, n,
+                       out.data_ptr())
+    return out
+
+
+def noise_step(seed: int, step: int, out, sigma=None, rho=None, w=None, base=None, stream: int = 0,
+               scenario0: int = 0):
+    """out = base + the step's disturbance, on the device (cmpc_noise_step, one
+    launch on torch's current stream; include/cmpc.h has the arithmetic).
+    out, and sigma, rho, w, base where given: contiguous float64 tensors (B, n)
+    on one device.  w is the AR(1) state, updated in place (needed with rho).
+    Returns out."""
+    import torch
+    if (not isinstance(out, torch.Tensor) or out.dim() != 2 or out.dtype != torch.float64 or not out.is_cuda
+            or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous float64 device tensor (B, n)")
+    B, n = int(out.shape[0]), int(out.shape[1])
+    key = noise_check(seed, step, B, n, stream, scenario0)
+    ptrs = [_noise_tensor(t, B, n, what, out.device)
+            for t, what in ((sigma, "sigma"), (rho, "rho"), (w, "w"), (base, "base"))]
+    noise_step_ptr(out.device.index, torch.cuda.current_stream(out.device).cuda_stream, key, step, B, n, *ptrs,
+                   out.data_ptr())
+    return out
 
 
 def certify_len(dims: CmpcDims) -> int:
@@ -839,6 +995,33 @@ class Context:
 
     def score_disable(self):
         check(self.lib.cmpc_score_disable(self._h), "cmpc_score_disable")
+
+    def score_ensemble(self, thresholds=None) -> dict:
+        """The device's reduction of the score record in force over the B
+        scenarios (cmpc_score_ensemble): {field: {stat: (S, rows) array}} with
+        the stats mean, std (population, about that mean), min, max, argmax
+        (the lowest scenario on a tie) and count (scenarios above the row's
+        threshold).  thresholds: None (every count 0), {field: a scalar or one
+        value per row of the field} (+inf for the fields left out), or
+        score_len values, one per record row."""
+        n = score_len(self.dims)
+        thr = None
+        if isinstance(thresholds, dict):
+            thr = np.full(n, np.inf)
+            fields = score_fields(self.dims)
+            for name, v in thresholds.items():
+                if name not in fields:
+                    raise ValueError(f"no score field named {name!r}")
+                sl = fields[name]
+                thr[sl] = np.broadcast_to(np.asarray(v, dtype=np.float64), (sl.stop - sl.start,))
+        elif thresholds is not None:
+            thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+            if thr.size != n:
+                raise ValueError(f"thresholds must hold score_len = {n} values, got {thr.size}")
+        out = np.zeros(n * self.dims.S * len(_abi.ENSEMBLE_STATS))
+        check(self.lib.cmpc_score_ensemble(self._h, dptr(thr) if thr is not None else None, dptr(out)),
+              "cmpc_score_ensemble")
+        return score_ensemble_unpack(self.dims, out)
 
     # -- results ---------------------------------------------------------
     def download(self):

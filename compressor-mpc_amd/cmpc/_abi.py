@@ -159,6 +159,9 @@ EXPORTS = (
     "cmpc_score_disable",
     "cmpc_certify_len", "cmpc_certify_field", "cmpc_certify_available", "cmpc_certify", "cmpc_certify_host",
     "cmpc_certify_device", "cmpc_certify_download", "cmpc_certify_summary",
+    "cmpc_score_ensemble",
+    "cmpc_noise_check", "cmpc_noise_check_params", "cmpc_noise_uniforms_host", "cmpc_noise_step_host",
+    "cmpc_noise_uniforms", "cmpc_noise_step",
 )
 
 # the fields of a slot's score record, in the record's order (cmpc_score_field
@@ -179,6 +182,20 @@ class CmpcCertifySummary(ctypes.Structure):
 
     def as_dict(self) -> dict:
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# the statistics of Context.score_ensemble, in the order cmpc_score_ensemble writes them
+ENSEMBLE_STATS = ("mean", "std", "min", "max", "argmax", "count")
+
+# the noise streams the closed loop uses (include/cmpc.h); the others are the caller's
+CMPC_NOISE_STREAM_MEASUREMENT = 0
+CMPC_NOISE_STREAM_INPUT = 1
+
+
+class CmpcNoiseKey(ctypes.Structure):
+    """cmpc_noise_key (include/cmpc.h)."""
+    _fields_ = [("seed", ctypes.c_uint64), ("stream", ctypes.c_uint32), ("scenario0", ctypes.c_uint32)]
+
 
 _lib = None
 
@@ -351,6 +368,17 @@ def load_library(path: str = LIB_PATH):
         "cmpc_certify_device": ([c_void], c_void),
         "cmpc_certify_download": ([c_void, P(dbl)], ctypes.c_int),
         "cmpc_certify_summary": ([c_void, dbl, P(CmpcCertifySummary)], ctypes.c_int),
+        "cmpc_score_ensemble": ([c_void, P(dbl), P(dbl)], ctypes.c_int),
+        "cmpc_noise_check": ([P(CmpcNoiseKey), ctypes.c_uint64, ctypes.c_int, ctypes.c_int], ctypes.c_int),
+        "cmpc_noise_check_params": ([ctypes.c_int, ctypes.c_int, P(dbl), P(dbl)], ctypes.c_int),
+        "cmpc_noise_uniforms_host": ([P(CmpcNoiseKey), ctypes.c_uint64, ctypes.c_int, ctypes.c_int, P(dbl)],
+                                     ctypes.c_int),
+        "cmpc_noise_step_host": ([P(CmpcNoiseKey), ctypes.c_uint64, ctypes.c_int, ctypes.c_int, P(dbl), P(dbl),
+                                  P(dbl), P(dbl), P(dbl)], ctypes.c_int),
+        "cmpc_noise_uniforms": ([ctypes.c_int, c_void, P(CmpcNoiseKey), ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
+                                 c_void], ctypes.c_int),
+        "cmpc_noise_step": ([ctypes.c_int, c_void, P(CmpcNoiseKey), ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
+                             c_void, c_void, c_void, c_void, c_void], ctypes.c_int),
         "cmpc_qp_solve_batch": ([ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(dbl),
                                  P(dbl), P(dbl), P(dbl), P(dbl), P(dbl), P(u32), ctypes.c_int,
                                  P(dbl), P(i32), P(i32), P(u32), P(ctypes.c_uint8), P(i32)],

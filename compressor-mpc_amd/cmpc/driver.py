@@ -130,6 +130,9 @@ class ClosedLoop:
         self._pp_sched = self._pm_sched = None  # their schedules, (B, T, 2) device
         if pressures is not None or model_pressures is not None:
             self.set_pressures(pressures, pressures if model_pressures is None else model_pressures)
+        self._noise = None         # set_noise: the seed, the device arrays and the scratch tensors
+        self._plant_offset = self.u_offset   # the plant's input offset in force (segment switches followed)
+        self.last_measurement = None
 
     def set_segments(self, segments, u_default):
         """The setup file's `simulation` segments ([(offset change, end time)],
@@ -144,7 +147,7 @@ class ClosedLoop:
         shape = (self.B, u_default.shape[-1])
         offs = [np.array(np.broadcast_to(u_default + np.asarray(d, dtype=np.float64), shape)) for d, _ in segments]
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
-        self.u_offset = t(offs[0])
+        self.u_offset = self._plant_offset = t(offs[0])
         self._sched = [(float(segments[i - 1][1]), t(offs[i])) for i in range(1, len(segments))]
 
     def set_setpoints(self, y_offset):
@@ -329,6 +332,72 @@ class ClosedLoop:
         self._score_target = self.torch.zeros(self.B * self.cfg.S, self.cfg.ny, dtype=self.torch.float64,
                                               device=self.dev)
 
+    def set_noise(self, seed, sigma_y=None, sigma_u=None, rho_u=None, scenario0: int = 0):
+        """Seeded measurement noise and input disturbances, a realisation per
+        scenario (cmpc.noise_step, include/cmpc.h has the arithmetic), for
+        Monte Carlo runs.  sigma_y: standard deviation per plant output;
+        sigma_u, rho_u: stationary standard deviation and AR(1) coefficient per
+        plant input (rho_u None: white); each (n,) or (B, n).  All three None
+        turns noise off.  scenario0: the global index of this batch's scenario
+        0, so a shard of a larger ensemble draws what its scenarios draw in the
+        whole (the draws do not depend on B).  In force, step k
+          - measures y_meas = y + sigma_y z (stream 0, step k) into a tensor of
+            its own, kept as self.last_measurement: the observers see y_meas,
+            while step() returns the true y and the scores score the true y;
+          - sets the plant's input offset to the offset in force (segment
+            switches followed) + w_k before the input is applied, w the AR(1)
+            (or white) draw of stream 1: the controller's own offset is
+            untouched, so this is an unmeasured disturbance.
+        initialize zeroes w and uses the true y(x0).  Arguments are checked
+        before anything is allocated.  With no noise set a step issues exactly
+        the calls it issues without this feature."""
+        from . import noise_check, noise_check_params
+        if sigma_y is None and sigma_u is None and rho_u is None:
+            if self._noise is not None and self._noise["su"] is not None:
+                self.sim.set_offset(self._plant_offset)
+            self._noise = None
+            self.last_measurement = None
+            return
+        if rho_u is not None and sigma_u is None:
+            raise ValueError("rho_u needs sigma_u")
+        no, ni = self.sim.no, self.sim.ni
+        noise_check(seed, 0, self.B, max(no, ni), 0, scenario0)
+        sy, _ = noise_check_params(self.B, no, sigma_y, None)
+        su, ru = noise_check_params(self.B, ni, sigma_u, rho_u)
+        torch = self.torch
+        t = lambda a: None if a is None else torch.from_numpy(a).to(self.dev)
+        new = lambda n: torch.zeros(self.B, n, dtype=torch.float64, device=self.dev)
+        self._noise = dict(seed=int(seed), scenario0=int(scenario0), sy=t(sy), su=t(su), ru=t(ru),
+                           y_meas=new(no) if sy is not None else None,
+                           w=new(ni) if ru is not None else None,
+                           offset=new(ni) if su is not None else None)
+        self.last_measurement = self._noise["y_meas"]
+
+    def _measure(self, y):
+        """The measurement the observers see: y, or y + sigma_y z of step self.k."""
+        nz = self._noise
+        if nz is None or nz["sy"] is None:
+            return y
+        from . import CMPC_NOISE_STREAM_MEASUREMENT, noise_step
+        return noise_step(nz["seed"], self.k, nz["y_meas"], sigma=nz["sy"], base=y,
+                          stream=CMPC_NOISE_STREAM_MEASUREMENT, scenario0=nz["scenario0"])
+
+    def _disturb(self):
+        """The plant's input offset of step self.k: the one in force + w_k."""
+        nz = self._noise
+        if nz is None or nz["su"] is None:
+            return
+        from . import CMPC_NOISE_STREAM_INPUT, noise_step
+        noise_step(nz["seed"], self.k, nz["offset"], sigma=nz["su"], rho=nz["ru"], w=nz["w"],
+                   base=self._plant_offset, stream=CMPC_NOISE_STREAM_INPUT, scenario0=nz["scenario0"])
+        self.sim.set_offset(nz["offset"])
+
+    def score_ensemble(self, thresholds=None) -> dict:
+        """Mean, std, min, max, argmax and count over the B scenarios of every
+        row of the score record, reduced on the device (Context.score_ensemble):
+        {field: {stat: (S, rows)}}."""
+        return self.ctx.score_ensemble(thresholds)
+
     def _score_step(self, y):
         """The instant's indices (enable_scores): one launch on the step's stream."""
         tgt = 0
@@ -378,6 +447,9 @@ class ClosedLoop:
         the first build and the cold InitializeQPProblem solves."""
         self.sim.reset(self.x0, self.u_offset, self.Ts)
         self.k = 0
+        self._plant_offset = self.u_offset
+        if self._noise is not None and self._noise["w"] is not None:
+            self._noise["w"].zero_()
         self._pressure_rows()
         y0 = self.sim.output()
         dx = 0 if dx_init is None else self.torch.from_numpy(np.ascontiguousarray(dx_init)).to(self.dev)
@@ -417,7 +489,7 @@ class ClosedLoop:
         # u_offset_) with the controller's own offset (fixed at Initialize; the
         # plant's may have stepped, see set_segments)
         self.sim.plant_input_offset(self.u_ctrl, self.u_offset, self.u_lin)
-        self.ctx.observe_step(self.u_lin.data_ptr(), y.data_ptr())
+        self.ctx.observe_step(self.u_lin.data_ptr(), self._measure(y).data_ptr())
         self._setpoint_window()
         self.ctx.build()
         self.ctx.iterate(self.K, CMPC_TRACE if trace else 0)
@@ -437,11 +509,13 @@ class ClosedLoop:
             self._score_step(y)
         # SetInput(u) through the delay line, then the plant over [t, t + Ts];
         # at the end of a segment's Integrate call: SetOffset and a new call
+        self._disturb()
         self.sim.set_input(self.u_ctrl)
         if self._sched and t_int >= self._sched[0][0] - 1e-9:
             self.t_seg = self._sched[0][0]
             self.seg_step = 0
-            self.sim.set_offset(self._sched.pop(0)[1])
+            self._plant_offset = self._sched.pop(0)[1]
+            self.sim.set_offset(self._plant_offset)
             self.sim.restart(self.Ts)
         else:
             self.sim.integrate(t_int, t_int + self.Ts, REF_EPS, REF_EPS)

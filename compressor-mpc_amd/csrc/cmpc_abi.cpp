@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "dispatch.h"
+#include "noise_body.h"
 
 namespace {
 
@@ -248,6 +249,15 @@ struct cmpc_ctx {
   std::vector<hipEvent_t> event_pool;  // reused so timing stays cheap in a timed loop
   double tot_ms[CMPC_KERNEL_COUNT] = {};
   int64_t launches[CMPC_KERNEL_COUNT] = {};
+  // ensemble statistics of the score record (cmpc_score_ensemble): the work
+  // buffer is allocated by the first call and released with the context
+  // (last, so that no other member's place in the context changes)
+  struct DeviceBuf {
+    void* p = nullptr;
+    ~DeviceBuf() {
+      if (p) (void)hipFree(p);
+    }
+  } score_ens_work;
 };
 
 namespace {
@@ -2900,6 +2910,181 @@ int cmpc_score_disable(cmpc_ctx* c) {
   c->score_on = false;
   c->score_k = 0;
   return 0;
+}
+
+// Ensemble statistics of the score record (include/cmpc.h, score_ensemble.hip).
+int cmpc_score_ensemble(cmpc_ctx* c, const double* thresholds, double* out) {
+  if (!c || !out) return fail("cmpc_score_ensemble: null argument");
+  if (!c->score_on) return fail("cmpc_score_ensemble: scoring is not enabled (cmpc_score_enable)");
+  const int len = cmpc_score_fields(c->d.ny, c->d.nu).len, S = c->d.S;
+  if (thresholds)
+    for (int f = 0; f < len; ++f)
+      if (std::isnan(thresholds[f]))
+        return fail("cmpc_score_ensemble: threshold of row " + std::to_string(f) + " is not a number");
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->score_ens_work.p) HIP_TRY(hipMalloc(&c->score_ens_work.p, cmpc_score_ensemble_bytes(len, S)));
+  void* work = c->score_ens_work.p;
+  if (thresholds)
+    HIP_TRY(hipMemcpyAsync(cmpc_score_ensemble_thresholds(work, len, S), thresholds, sizeof(double) * len,
+                           hipMemcpyHostToDevice, c->stream));
+  if (cmpc_launch_score_ensemble(c->score_rec, len, c->d.B, S, thresholds != nullptr, work, c->stream))
+    return plan_mismatch("score ensemble");
+  if (check_launch("score ensemble kernels")) return -1;
+  HIP_TRY(hipMemcpyAsync(out, work, sizeof(double) * (size_t)len * S * kScoreEnsembleStats, hipMemcpyDeviceToHost,
+                         c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// Seeded per-scenario noise (include/cmpc.h, noise_body.h, noise.hip).
+int cmpc_noise_check(const cmpc_noise_key* key, uint64_t step, int B, int n) {
+  if (!key) return fail("cmpc_noise: null key");
+  if (B < 1) return fail("cmpc_noise: B must be >= 1");
+  if (n < 1) return fail("cmpc_noise: n must be >= 1");
+  if (step >> 32) return fail("cmpc_noise: step must be below 2^32 (the counter's word)");
+  if ((uint64_t)key->scenario0 + (uint64_t)B > (1ull << 32))
+    return fail("cmpc_noise: scenario0 + B must be at most 2^32 (the counter's word)");
+  if (((uint64_t)B * (uint64_t)((n + 1) / 2) + 63) / 64 > 0x7fffffffull)
+    return fail("cmpc_noise: B * ceil(n / 2) is more than one launch covers");
+  return 0;
+}
+
+int cmpc_noise_check_params(int B, int n, const double* sigma, const double* rho) {
+  if (B < 1 || n < 1) return fail("cmpc_noise_check_params: B and n must be >= 1");
+  const size_t m = (size_t)B * n;
+  for (size_t e = 0; sigma && e < m; ++e)
+    if (!std::isfinite(sigma[e]) || sigma[e] < 0)
+      return fail("cmpc_noise_check_params: scenario " + std::to_string(e / n) + ", channel " + std::to_string(e % n) +
+                  ": sigma must be finite and >= 0");
+  for (size_t e = 0; rho && e < m; ++e)
+    if (!(rho[e] >= -1.0 && rho[e] <= 1.0))
+      return fail("cmpc_noise_check_params: scenario " + std::to_string(e / n) + ", channel " + std::to_string(e % n) +
+                  ": rho must be inside [-1, 1]");
+  return 0;
+}
+
+static NoiseKeyWords noise_words(const cmpc_noise_key* key) {
+  return NoiseKeyWords{(uint32_t)key->seed, (uint32_t)(key->seed >> 32), key->stream, key->scenario0};
+}
+
+int cmpc_noise_uniforms_host(const cmpc_noise_key* key, uint64_t step, int B, int n, double* u) {
+  if (cmpc_noise_check(key, step, B, n)) return -1;
+  if (!u) return fail("cmpc_noise_uniforms_host: null u");
+  const NoiseKeyWords k = noise_words(key);
+  const int np = (n + 1) / 2;
+  for (int b = 0; b < B; ++b)
+    for (int j = 0; j < np; ++j) {
+      double* o = u + ((size_t)b * np + j) * 2;
+      cmpc_noise_uniforms(k, key->scenario0 + (uint32_t)b, (uint32_t)step, (uint32_t)j, o, o + 1);
+    }
+  return 0;
+}
+
+int cmpc_noise_step_host(const cmpc_noise_key* key, uint64_t step, int B, int n, const double* sigma,
+                         const double* rho, double* w, const double* base, double* out) {
+  if (cmpc_noise_check(key, step, B, n)) return -1;
+  if (!out) return fail("cmpc_noise_step_host: null out");
+  if (rho && !w) return fail("cmpc_noise_step_host: rho needs the AR(1) state w");
+  const NoiseKeyWords k = noise_words(key);
+  const int np = (n + 1) / 2;
+  for (int b = 0; b < B; ++b)
+    for (int j = 0; j < np; ++j) {
+      double u1, u2, z0, z1;
+      cmpc_noise_uniforms(k, key->scenario0 + (uint32_t)b, (uint32_t)step, (uint32_t)j, &u1, &u2);
+      cmpc_noise_normals(u1, u2, &z0, &z1);
+      const size_t e = (size_t)b * n + 2 * (size_t)j;
+      cmpc_noise_element(z0, e, sigma, rho, w, base, out);
+      if (2 * j + 1 < n) cmpc_noise_element(z1, e + 1, sigma, rho, w, base, out);
+    }
+  return 0;
+}
+
+// cmpc_bind_state's check of a device pointer (device_ptr_ok) without a
+// context: a device allocation on `device` that holds `bytes` from p on,
+// 8-byte aligned.  The last pointers that passed are remembered per host
+// thread, as a context remembers its own: the queries cost host time per call.
+static bool noise_ptr_ok(int device, const void* p, size_t bytes) {
+  struct Entry {
+    int dev;
+    const void* p;
+    size_t bytes;
+  };
+  static thread_local Entry cache[16];
+  static thread_local int n = 0;
+  if (reinterpret_cast<uintptr_t>(p) % 8) return false;
+  for (int i = 0; i < n && i < 16; ++i)
+    if (cache[i].dev == device && cache[i].p == p && cache[i].bytes >= bytes) return true;
+  hipPointerAttribute_t a;
+  if (hipPointerGetAttributes(&a, p) != hipSuccess || a.type != hipMemoryTypeDevice || a.device != device) {
+    (void)hipGetLastError();  // a failed pointer query is not a later launch's error
+    return false;
+  }
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) == hipSuccess && base &&
+      (uintptr_t)p + bytes > (uintptr_t)base + size)
+    return false;
+  cache[n % 16] = Entry{device, p, bytes};
+  ++n;
+  return true;
+}
+
+static int noise_device(int device) {
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device < 0 || device >= ndev) return fail("cmpc_noise: no such HIP device");
+  HIP_TRY(hipSetDevice(device));
+  return 0;
+}
+
+int cmpc_noise_uniforms(int device, void* stream, const cmpc_noise_key* key, uint64_t step, int B, int n,
+                        double* u_dev) {
+  if (cmpc_noise_check(key, step, B, n)) return -1;
+  if (!u_dev) return fail("cmpc_noise_uniforms: null u");
+  if (noise_device(device)) return -1;
+  const int np = (n + 1) / 2;
+  if (!noise_ptr_ok(device, u_dev, sizeof(double) * (size_t)B * np * 2))
+    return fail("cmpc_noise_uniforms: u is not an 8-byte aligned device allocation of B * ceil(n / 2) * 2 doubles "
+                "on the device");
+  NoiseParams P{};
+  const NoiseKeyWords k = noise_words(key);
+  P.k0 = k.k0, P.k1 = k.k1, P.stream = k.stream, P.scenario0 = k.scenario0;
+  P.step = (uint32_t)step;
+  P.B = B, P.n = n, P.np = np;
+  P.u = u_dev;
+  if (cmpc_launch_noise_uniforms(P, stream)) return plan_mismatch("noise uniforms");
+  return check_launch("noise uniforms kernel");
+}
+
+int cmpc_noise_step(int device, void* stream, const cmpc_noise_key* key, uint64_t step, int B, int n,
+                    const double* sigma_dev, const double* rho_dev, double* w_dev, const double* base_dev,
+                    double* out_dev) {
+  if (cmpc_noise_check(key, step, B, n)) return -1;
+  if (!out_dev) return fail("cmpc_noise_step: null out");
+  if (rho_dev && !w_dev) return fail("cmpc_noise_step: rho needs the AR(1) state w");
+  if (noise_device(device)) return -1;
+  const size_t bytes = sizeof(double) * (size_t)B * n;
+  const struct {
+    const void* p;
+    const char* name;
+  } ptrs[] = {{sigma_dev, "sigma"}, {rho_dev, "rho"}, {rho_dev ? w_dev : nullptr, "w"}, {base_dev, "base"},
+              {out_dev, "out"}};
+  for (const auto& a : ptrs)
+    if (a.p && !noise_ptr_ok(device, a.p, bytes))
+      return fail(std::string("cmpc_noise_step: ") + a.name +
+                  " is not an 8-byte aligned device allocation of B * n doubles on the device");
+  NoiseParams P{};
+  const NoiseKeyWords k = noise_words(key);
+  P.k0 = k.k0, P.k1 = k.k1, P.stream = k.stream, P.scenario0 = k.scenario0;
+  P.step = (uint32_t)step;
+  P.B = B, P.n = n, P.np = (n + 1) / 2;
+  P.sigma = sigma_dev;
+  P.rho = rho_dev;
+  P.w = rho_dev ? w_dev : nullptr;
+  P.base = base_dev;
+  P.out = out_dev;
+  if (cmpc_launch_noise_step(P, stream)) return plan_mismatch("noise step");
+  return check_launch("noise kernel");
 }
 
 int cmpc_enable_timing(cmpc_ctx* c, int enable) {

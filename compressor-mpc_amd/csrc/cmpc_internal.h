@@ -376,6 +376,36 @@ int cmpc_launch_certify_summary(const double* rec, int nqp, int nV, double tol, 
 void cmpc_certify_summary_unpack(const void* work_head, cmpc_certify_summary_t* out);
 constexpr size_t kCertifySummaryHead = 64;  // bytes of the head (>= the partial's size)
 
+// Seeded per-scenario noise (noise.hip, cmpc_noise_*): the
+// draw's arithmetic is noise_body.h's, shared with the host entry points.
+struct NoiseParams {
+  uint32_t k0, k1, stream, scenario0;  // seed low and high words, stream, first global scenario
+  uint32_t step;
+  int B, n, np;          // np = ceil(n / 2) Box-Muller pairs per scenario
+  const double* sigma;   // B * n, or null: 1
+  const double* rho;     // B * n, or null: white
+  double* w;             // B * n AR(1) state (with rho)
+  const double* base;    // B * n, or null: 0
+  double* out;           // B * n
+  double* u;             // B * np * 2 uniforms (cmpc_launch_noise_uniforms)
+};
+// one lane per (scenario, pair), 64-lane workgroups; -1: more workgroups than a grid holds
+int cmpc_launch_noise_step(const NoiseParams& P, void* stream);
+int cmpc_launch_noise_uniforms(const NoiseParams& P, void* stream);
+
+// Ensemble statistics of the score record (score_ensemble.hip,
+// cmpc_score_ensemble): per record row f and sub-controller s over the B
+// scenarios, kScoreEnsembleStats doubles [mean, std, min, max, argmax, count]
+// at head[(f * S + s) * kScoreEnsembleStats].  `work` holds
+// cmpc_score_ensemble_bytes(len, S) bytes: the head (what the host copies),
+// then the thresholds (len doubles, read where has_thr), then the partials.
+constexpr int kScoreEnsembleStats = 6;
+size_t cmpc_score_ensemble_bytes(int len, int S);
+// the device address of the thresholds inside `work`
+double* cmpc_score_ensemble_thresholds(void* work, int len, int S);
+// three launches: partials per block, centred squares per block, a wave per row over both
+int cmpc_launch_score_ensemble(const double* rec, int len, int B, int S, bool has_thr, void* work, void* stream);
+
 // Standalone batched solver (parity / KKT tests).  G (nqp * n * nvo) and d
 // (nqp * nvo) non-null: the Jacobi iteration's map-form solve with g = f + G d
 // (cmpc_qp_solve_batch_map); g is f then.

@@ -726,6 +726,90 @@ double* cmpc_certify_device(cmpc_ctx* ctx);
 int cmpc_certify_download(cmpc_ctx* ctx, double* record);
 int cmpc_certify_summary(cmpc_ctx* ctx, double tol, cmpc_certify_summary_t* out);
 
+/* Ensemble statistics of the score record (score_ensemble.hip, DESIGN.md
+ * §3.17): what a Monte Carlo run reads in place of the len*B*S record.
+ *
+ * cmpc_score_ensemble: for every row f of the record in force (own or bound,
+ *   cmpc_score_bind) and every sub-controller s, over the B scenarios' values
+ *   x_b = record[f*B*S + b*S + s], six doubles at out[(f*S + s)*6]:
+ *     0 mean    sum x_b / B
+ *     1 std     sqrt(sum (x_b - mean)^2 / B): the population value about that
+ *               mean, from a second pass over the record
+ *     2 min     3 max
+ *     4 argmax  the scenario of the maximum, the lowest on a tie
+ *     5 count   scenarios with x_b > thresholds[f]; 0 with thresholds NULL
+ *   thresholds: len host doubles or NULL; out: len*S*6 host doubles.  Three
+ *   small launches (partials per block by wave shuffles and LDS, a wave per
+ *   row over the partials, no floating-point atomics), one copy, and a stream
+ *   synchronisation.  min, max, argmax and count equal the same reduction of
+ *   the downloaded record exactly; mean and std are sums in a fixed order for
+ *   a given B.  It reads the record and changes nothing but its own work
+ *   buffer, allocated by the first call.  Refused before cmpc_score_enable
+ *   and for a threshold that is not a number. */
+int cmpc_score_ensemble(cmpc_ctx* ctx, const double* thresholds, double* out);
+
+/* Seeded per-scenario noise and disturbances (noise_body.h, noise.hip,
+ * DESIGN.md §3.17): normal draws that are a pure function of (seed, stream,
+ * global scenario, step, channel), so a run is reproducible from its seed and
+ * the same however the scenarios are cut into batches or shards: batch b of a
+ * shard that starts at global scenario scenario0 draws what scenario
+ * scenario0 + b of the whole ensemble draws.  There is no generator state.
+ *
+ *   bits      Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants
+ *             0x9E3779B9, 0xBB67AE85), key (seed low 32, seed high 32), counter
+ *             (scenario0 + b, step, pair j = c / 2, stream)
+ *   uniforms  k1 = (x0 >> 5) 2^26 + (x1 >> 6), k2 likewise from x2 and x3;
+ *             u1 = (k1 + 1) 2^-53 in (0, 1], u2 = k2 2^-53 in [0, 1)
+ *   normals   r = sqrt(-2 log u1); channel 2j draws z = r cospi(2 u2), channel
+ *             2j + 1 z = r sinpi(2 u2); with n odd the last sine is dropped
+ *   element   e = b*n + c, s = sigma ? sigma[e] : 1
+ *             rho given:  g = sqrt(1 - rho[e] rho[e]) s
+ *                         w[e] = rho[e] w[e] + g z;  d = w[e]
+ *                         (an AR(1) of stationary standard deviation s; the
+ *                         state w is the caller's and starts where the caller
+ *                         puts it)
+ *             rho NULL:   d = s z
+ *             out[e] = d == 0 ? base[e] : base[e] + d   (a NULL base counts as
+ *             0): a zero sigma reproduces base bit for bit
+ * Products and sums are separate operations in that order, so given z a
+ * float64 host model reproduces w and out bit for bit.
+ *
+ * Streams: CMPC_NOISE_STREAM_MEASUREMENT (0) and CMPC_NOISE_STREAM_INPUT (1)
+ * are the closed loop's (cmpc.driver.ClosedLoop.set_noise); the others are the
+ * caller's.  All arrays are B*n doubles, row b the scenario's n channels; u is
+ * B*ceil(n/2)*2 doubles, [u1, u2] of pair j of scenario b at (b*ceil(n/2) + j)*2.
+ *
+ * cmpc_noise_check: host only, the argument check of every entry point.
+ *   Refused (-1, cmpc_last_error names the cause): NULL key, B < 1, n < 1,
+ *   step >= 2^32, scenario0 + B > 2^32 (each is one word of the counter).
+ * cmpc_noise_check_params: host only, over host arrays (either may be NULL):
+ *   sigma finite and >= 0, rho inside [-1, 1].  The step entry points do not
+ *   read the values to check them: that is the caller's, with this function.
+ * cmpc_noise_uniforms_host, cmpc_noise_step_host: the same arithmetic on host
+ *   arrays; no device is touched.
+ * cmpc_noise_uniforms, cmpc_noise_step: one launch on `stream` of `device`,
+ *   asynchronous; every pointer is checked as cmpc_bind_state checks its own
+ *   (a device allocation of the array's size on that device, 8-byte aligned).
+ *   Also refused: NULL out (or u), rho without w.  sigma, rho, base may be
+ *   NULL; w is read only with rho.  out may be base (in place). */
+#define CMPC_NOISE_STREAM_MEASUREMENT 0u
+#define CMPC_NOISE_STREAM_INPUT 1u
+typedef struct cmpc_noise_key {
+  uint64_t seed;
+  uint32_t stream;
+  uint32_t scenario0;
+} cmpc_noise_key;
+int cmpc_noise_check(const cmpc_noise_key* key, uint64_t step, int B, int n);
+int cmpc_noise_check_params(int B, int n, const double* sigma, const double* rho);
+int cmpc_noise_uniforms_host(const cmpc_noise_key* key, uint64_t step, int B, int n, double* u);
+int cmpc_noise_step_host(const cmpc_noise_key* key, uint64_t step, int B, int n, const double* sigma,
+                         const double* rho, double* w, const double* base, double* out);
+int cmpc_noise_uniforms(int device, void* stream, const cmpc_noise_key* key, uint64_t step, int B, int n,
+                        double* u_dev);
+int cmpc_noise_step(int device, void* stream, const cmpc_noise_key* key, uint64_t step, int B, int n,
+                    const double* sigma_dev, const double* rho_dev, double* w_dev, const double* base_dev,
+                    double* out_dev);
+
 /* Per-kernel device time (HIP events stamped by the kernel's own dispatch,
  * opt-in).  enable: 0 off, 1 every kernel, or an OR of CMPC_TIME_ONLY(k)
  * to time only those kernels (the others launch without events). */
