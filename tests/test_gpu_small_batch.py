@@ -13,6 +13,7 @@ import pytest
 import cmpc
 from cmpc.configs import reference_setup
 from cmpc.synthetic import synthetic_batch
+from jacobi_ref import oracle_jacobi as _oracle_jacobi
 
 pytestmark = pytest.mark.gpu
 
@@ -219,41 +220,6 @@ def test_gpu_fused_step_equals_split_step(plant, ctype, p, K, B):
             assert np.array_equal(x, y), (step, name)
     print(f"{plant}-{ctype} p={p} B={B}: ok {np.mean(split[-1][1] == 0):.3f}, "
           f"changes/QP {split[-1][7].sum() / len(split[-1][1]):.3f}")
-
-
-def _oracle_jacobi(cfg, arr, H, f, G, u_old, du_old, ws, K):
-    """The Jacobi loop of one step on the device's own (H, f, G) with the
-    oracle's map-form solve (or_qp.c step A, version 3): per iteration each
-    sub-controller solves with d = the other sub-controllers' previous plans
-    in G's column order (controller-major inside each move,
-    include/nerve_center.h:283-285)."""
-    import _oracle as O
-    S, nu, m = cfg.S, cfg.nu, cfg.m
-    nV = nu * m
-    nqp = H.shape[0]
-    dprev = du_old.reshape(nqp, nV).copy()
-    ws = ws.copy()
-    st = np.zeros(nqp, np.int32); nw = np.zeros(nqp, np.int32)
-    tr = np.full((nqp, K, 16), 0xFF, np.uint8); ntr = np.zeros((nqp, K), np.int32)
-    for k in range(K):
-        dnew = np.zeros_like(dprev)
-        for q in range(nqp):
-            b, s = divmod(q, S)
-            d = np.zeros((S - 1) * nV)
-            for rk in range(S - 1):
-                s2 = rk + (rk >= s)
-                for mv in range(m):
-                    d[mv * (S - 1) * nu + rk * nu: mv * (S - 1) * nu + rk * nu + nu] = \
-                        dprev[b * S + s2, mv * nu:(mv + 1) * nu]
-            lo = np.tile(arr.lower[s] - u_old[q, :nu], m); hi = np.tile(arr.upper[s] - u_old[q, :nu], m)
-            rlo = np.tile(arr.rate_lower[s], m); rhi = np.tile(arr.rate_upper[s], m)
-            x, info = O.qp_solve_map(H[q], f[q], G[q], d, lo, hi, rlo, rhi, nu, int(ws[q]))
-            dnew[q] = x
-            ws[q] = info.ws
-            st[q] = info.status; nw[q] = info.nchg
-            tr[q, k] = np.frombuffer(bytes(info.trace), np.uint8); ntr[q, k] = info.ntrace
-        dprev = dnew
-    return dprev, st, nw, ws, tr, ntr
 
 
 JCASES = [  # plant, controller, p, m, K, B scenarios
