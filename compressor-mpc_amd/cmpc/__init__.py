@@ -40,7 +40,8 @@ __all__ = ["Context", "ControllerConfig", "SetupFile", "reference_config", "refe
            "certify_len", "certify_fields", "certify_available", "score_ensemble_unpack",
            "noise_key", "noise_check", "noise_check_params", "noise_uniforms_host", "noise_step_host",
            "noise_uniforms", "noise_step", "noise_uniforms_ptr", "noise_step_ptr",
-           "CMPC_NOISE_STREAM_MEASUREMENT", "CMPC_NOISE_STREAM_INPUT"]
+           "CMPC_NOISE_STREAM_MEASUREMENT", "CMPC_NOISE_STREAM_INPUT",
+           "quantile_check", "quantile_rank", "quantile_value", "quantiles_host", "envelope_check", "envelope_len"]
 
 
 def layout_of(dims: CmpcDims) -> CmpcLayout:
@@ -145,6 +146,88 @@ def score_ensemble_unpack(dims: CmpcDims, flat) -> dict:
             v = np.ascontiguousarray(a[sl, :, k].T)
             out[name][stat] = v.astype(np.int64) if stat in ("argmax", "count") else v
     return out
+
+
+def quantile_check(B: int, levels) -> np.ndarray:
+    """The argument check of the quantile entry points (cmpc_quantile_check,
+    host only); raises with the library's message.  Returns the levels."""
+    lv = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    check(load_library().cmpc_quantile_check(int(B), int(lv.size), dptr(lv) if lv.size else None),
+          "cmpc_quantile_check")
+    return lv
+
+
+def quantile_rank(B: int, level: float):
+    """(k_lo, k_hi, g) of a level among B values (cmpc_quantile_rank, host only):
+    h = level (B - 1), k_lo = floor(h), g = h - k_lo, k_hi = k_lo + (g > 0)."""
+    lo, hi, g = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_double()
+    check(load_library().cmpc_quantile_rank(int(B), float(level), ctypes.byref(lo), ctypes.byref(hi),
+                                            ctypes.byref(g)), "cmpc_quantile_rank")
+    return lo.value, hi.value, g.value
+
+
+def quantile_value(x_lo, x_hi, g):
+    """The value between two order statistics (cmpc_quantile_value, host only):
+    x_lo where they are equal, else x_lo + d g for g < 0.5 and x_hi - d (1 - g)
+    otherwise, d = x_hi - x_lo.  Arrays broadcast; scalars give a float."""
+    fn = load_library().cmpc_quantile_value
+    a, b, t = np.broadcast_arrays(np.asarray(x_lo, dtype=np.float64), np.asarray(x_hi, dtype=np.float64),
+                                  np.asarray(g, dtype=np.float64))
+    out = np.array([fn(float(p), float(q), float(r)) for p, q, r in zip(a.ravel(), b.ravel(), t.ravel())],
+                   dtype=np.float64).reshape(a.shape)
+    return out if out.ndim else float(out)
+
+
+def quantiles_host(x, levels) -> dict:
+    """Exact order statistics over axis 1 of a (len, B, S) host array (or (B, C):
+    len = 1, S = C) by the library's own selection on host memory
+    (cmpc_quantiles_host, no device): {"lo", "hi", "arg", "value"}, each
+    (n_levels, len, S); arg (int64) is the lowest b holding lo."""
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    if a.ndim == 2:
+        a = a[None]
+    if a.ndim != 3:
+        raise ValueError(f"x must be (len, B, S) or (B, C), got {a.shape}")
+    n, B, S = a.shape
+    lv = quantile_check(B, levels)
+    if n < 1 or S < 1:
+        raise ValueError(f"x must not be empty, got {a.shape}")
+    out = np.zeros((n, S, lv.size, 3))
+    check(load_library().cmpc_quantiles_host(dptr(a), n, B, S, int(lv.size), dptr(lv), dptr(out)),
+          "cmpc_quantiles_host")
+    return _quantiles_unpack(out, B, lv)
+
+
+def _quantiles_unpack(out, B: int, lv) -> dict:
+    """(rows, S, n_levels, 3) of [x_lo, x_hi, arg] -> the dict of (n_levels, rows, S)."""
+    lo, hi, arg = (np.ascontiguousarray(out[..., k].transpose(2, 0, 1)) for k in range(3))
+    g = np.array([quantile_rank(B, q)[2] for q in lv])
+    return {"lo": lo, "hi": hi, "arg": arg.astype(np.int64), "value": quantile_value(lo, hi, g[:, None, None])}
+
+
+def envelope_check(dims: CmpcDims, n_outputs: int, t_cap: int, levels=(), thresholds=None):
+    """The argument check of Context.envelope_enable without a context
+    (cmpc_envelope_check, host only); raises with the library's message.
+    Returns (levels, thresholds) as arrays (thresholds None stays None)."""
+    lv = np.ascontiguousarray(levels, dtype=np.float64).reshape(-1)
+    th = None
+    if thresholds is not None:
+        th = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        if th.size != int(n_outputs) + dims.nu_tot:
+            raise ValueError(f"thresholds must hold n_outputs + nu_tot = {int(n_outputs) + dims.nu_tot} values, "
+                             f"got {th.size}")
+    check(load_library().cmpc_envelope_check(ctypes.byref(dims), int(n_outputs), int(t_cap), int(lv.size),
+                                             dptr(lv) if lv.size else None, dptr(th) if th is not None else None),
+          "cmpc_envelope_check")
+    return lv, th
+
+
+def envelope_len(dims: CmpcDims, n_outputs: int, n_levels: int) -> int:
+    """Doubles per step row of the envelope, (n_outputs + nu_tot) (6 + 2
+    n_levels) (cmpc_envelope_len, host only)."""
+    n = load_library().cmpc_envelope_len(ctypes.byref(dims), int(n_outputs), int(n_levels))
+    check(min(n, 0), "cmpc_envelope_len")
+    return n
 
 
 def noise_key(seed: int, stream: int = 0, scenario0: int = 0) -> CmpcNoiseKey:
@@ -1022,6 +1105,59 @@ class Context:
         check(self.lib.cmpc_score_ensemble(self._h, dptr(thr) if thr is not None else None, dptr(out)),
               "cmpc_score_ensemble")
         return score_ensemble_unpack(self.dims, out)
+
+    def score_quantiles(self, levels) -> dict:
+        """Exact quantiles over the B scenarios of every row of the score
+        record in force, selected on the device (cmpc_score_quantiles):
+        {field: {"lo", "hi", "arg", "value": (n_levels, S, rows)}} with lo and
+        hi the order statistics at the level's two ranks (quantile_rank), arg
+        (int64) the lowest scenario holding lo, and value = quantile_value(lo,
+        hi, g): numpy's quantile on finite data."""
+        lv = quantile_check(self.dims.B, levels)
+        n, S = score_len(self.dims), self.dims.S
+        out = np.zeros((n, S, lv.size, 3))
+        check(self.lib.cmpc_score_quantiles(self._h, int(lv.size), dptr(lv), dptr(out)), "cmpc_score_quantiles")
+        q = _quantiles_unpack(out, self.dims.B, lv)                # (n_levels, len, S)
+        return {name: {k: np.ascontiguousarray(v[:, sl, :].transpose(0, 2, 1)) for k, v in q.items()}
+                for name, sl in score_fields(self.dims).items()}
+
+    # -- the ensemble's envelope per step (include/cmpc.h, cmpc_envelope_*) --
+    def envelope_enable(self, n_outputs: int, t_cap: int, levels=(), thresholds=None):
+        """Record, per step, the six ensemble statistics and the quantile pairs
+        of `levels` (none: the statistics only) of every plant output and
+        control input over the B scenarios; thresholds: one per channel
+        (n_outputs + nu_tot) for the counts, or None."""
+        lv, th = envelope_check(self.dims, n_outputs, t_cap, levels, thresholds)
+        check(self.lib.cmpc_envelope_enable(self._h, int(n_outputs), int(t_cap), int(lv.size),
+                                            dptr(lv) if lv.size else None, dptr(th) if th is not None else None),
+              "cmpc_envelope_enable")
+        self._env = (int(n_outputs), int(t_cap), lv)
+
+    def envelope_step(self, y_ptr: int, u_control_ptr: int = 0):
+        """One row from the device arrays y (B, n_outputs) and u_control (B,
+        nu_tot) or 0 (cmpc_envelope_step): launches on the context's stream."""
+        check(self.lib.cmpc_envelope_step(self._h, ctypes.c_void_p(y_ptr or None),
+                                          ctypes.c_void_p(u_control_ptr or None)), "cmpc_envelope_step")
+
+    def envelope_reset(self):
+        check(self.lib.cmpc_envelope_reset(self._h), "cmpc_envelope_reset")
+
+    def envelope_bind(self, device_ptr: int = 0):
+        """Keep the rows in a device buffer of t_cap * envelope_len f64 (0: the context's own)."""
+        check(self.lib.cmpc_envelope_bind(self._h, ctypes.c_void_p(device_ptr or None)), "cmpc_envelope_bind")
+
+    def envelope_download(self):
+        """(rows (t_cap, channels, 6 + 2 n_levels), steps recorded)."""
+        no, t_cap, lv = getattr(self, "_env", (0, 0, np.zeros(0)))
+        rows = np.zeros((t_cap, no + self.cfg.nu_tot if t_cap else 0, 6 + 2 * lv.size))
+        n = np.zeros(1, np.int32)
+        check(self.lib.cmpc_envelope_download(self._h, dptr(rows) if rows.size else None, iptr(n)),
+              "cmpc_envelope_download")
+        return rows, int(n[0])
+
+    def envelope_disable(self):
+        check(self.lib.cmpc_envelope_disable(self._h), "cmpc_envelope_disable")
+        self._env = (0, 0, np.zeros(0))
 
     # -- results ---------------------------------------------------------
     def download(self):

@@ -162,6 +162,9 @@ EXPORTS = (
     "cmpc_score_ensemble",
     "cmpc_noise_check", "cmpc_noise_check_params", "cmpc_noise_uniforms_host", "cmpc_noise_step_host",
     "cmpc_noise_uniforms", "cmpc_noise_step",
+    "cmpc_quantile_check", "cmpc_quantile_rank", "cmpc_quantiles_host", "cmpc_score_quantiles",
+    "cmpc_envelope_check", "cmpc_envelope_len", "cmpc_envelope_enable", "cmpc_envelope_step",
+    "cmpc_envelope_reset", "cmpc_envelope_bind", "cmpc_envelope_download", "cmpc_envelope_disable",
 )
 
 # the fields of a slot's score record, in the record's order (cmpc_score_field
@@ -186,6 +189,9 @@ class CmpcCertifySummary(ctypes.Structure):
 
 # the statistics of Context.score_ensemble, in the order cmpc_score_ensemble writes them
 ENSEMBLE_STATS = ("mean", "std", "min", "max", "argmax", "count")
+
+# levels per quantile call (include/cmpc.h)
+CMPC_QUANTILE_MAX_LEVELS = 8
 
 # the noise streams the closed loop uses (include/cmpc.h); the others are the caller's
 CMPC_NOISE_STREAM_MEASUREMENT = 0
@@ -379,6 +385,21 @@ def load_library(path: str = LIB_PATH):
                                  c_void], ctypes.c_int),
         "cmpc_noise_step": ([ctypes.c_int, c_void, P(CmpcNoiseKey), ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
                              c_void, c_void, c_void, c_void, c_void], ctypes.c_int),
+        "cmpc_quantile_check": ([ctypes.c_int, ctypes.c_int, P(dbl)], ctypes.c_int),
+        "cmpc_quantile_rank": ([ctypes.c_int, dbl, P(i32), P(i32), P(dbl)], ctypes.c_int),
+        "cmpc_quantile_value": ([dbl, dbl, dbl], dbl),   # (returns a double: not in EXPORTS' pattern)
+        "cmpc_quantiles_host": ([P(dbl), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(dbl), P(dbl)],
+                                ctypes.c_int),
+        "cmpc_score_quantiles": ([c_void, ctypes.c_int, P(dbl), P(dbl)], ctypes.c_int),
+        "cmpc_envelope_check": ([P(CmpcDims), ctypes.c_int, ctypes.c_int, ctypes.c_int, P(dbl), P(dbl)],
+                                ctypes.c_int),
+        "cmpc_envelope_len": ([P(CmpcDims), ctypes.c_int, ctypes.c_int], ctypes.c_int),
+        "cmpc_envelope_enable": ([c_void, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(dbl), P(dbl)], ctypes.c_int),
+        "cmpc_envelope_step": ([c_void, c_void, c_void], ctypes.c_int),
+        "cmpc_envelope_reset": ([c_void], ctypes.c_int),
+        "cmpc_envelope_bind": ([c_void, c_void], ctypes.c_int),
+        "cmpc_envelope_download": ([c_void, P(dbl), P(i32)], ctypes.c_int),
+        "cmpc_envelope_disable": ([c_void], ctypes.c_int),
         "cmpc_qp_solve_batch": ([ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(dbl),
                                  P(dbl), P(dbl), P(dbl), P(dbl), P(dbl), P(u32), ctypes.c_int,
                                  P(dbl), P(i32), P(i32), P(u32), P(ctypes.c_uint8), P(i32)],

@@ -112,6 +112,7 @@ class ClosedLoop:
         for s in range(S):
             self.ctx.set_observer(s, M[s])
         self._scores = False    # enable_scores: closed-loop indices per QP slot
+        self._envelope = False  # enable_envelope: the ensemble's spread per step
         self._dy_ref = None     # the setpoint offsets in force, (B*S, ny) host
         if y_offset is not None:
             self.set_setpoints(y_offset)
@@ -398,6 +399,48 @@ class ClosedLoop:
         {field: {stat: (S, rows)}}."""
         return self.ctx.score_ensemble(thresholds)
 
+    def score_quantiles(self, levels) -> dict:
+        """Exact quantiles over the B scenarios of every row of the score
+        record, selected on the device (Context.score_quantiles): {field:
+        {"lo", "hi", "arg", "value": (n_levels, S, rows)}}."""
+        return self.ctx.score_quantiles(levels)
+
+    def enable_envelope(self, steps: int, levels=(0.05, 0.5, 0.95), thresholds=None):
+        """Record, at each of the first `steps` instants after initialize, how
+        the ensemble is spread (Context.envelope_*, include/cmpc.h): per plant
+        output and control input the mean, std, min, max, argmax and the count
+        of scenarios above the channel's threshold (thresholds: n_outputs +
+        nu_tot values or None), and the quantile bands of `levels`.  A step
+        then adds a few small launches where the scores' launch sits, on the
+        true y and u_ctrl; nothing is copied to the host before envelope().
+        Independent of enable_scores.  Arguments are refused before anything
+        is allocated."""
+        self.ctx.envelope_enable(self.sim.no, int(steps), levels, thresholds)
+        self._envelope = True
+
+    def envelope(self):
+        """(t (n,), {"y": {...}, "u": {...}}) for the n instants recorded so
+        far: per group the statistics mean, std, min, max, argmax, count as (n,
+        channels) arrays (argmax and count int64) and lo, hi, value as (n,
+        n_levels, channels)."""
+        from . import _abi, quantile_rank, quantile_value
+        rows, n = self.ctx.envelope_download()
+        rows = rows[:n]
+        no, lv = self.sim.no, self.ctx._env[2]
+        g = np.array([quantile_rank(self.B, q)[2] for q in lv]).reshape(1, -1, 1)
+        out = {}
+        for name, a in (("y", rows[:, :no]), ("u", rows[:, no:])):
+            d = {}
+            for k, stat in enumerate(_abi.ENSEMBLE_STATS):
+                v = np.ascontiguousarray(a[:, :, k])
+                d[stat] = v.astype(np.int64) if stat in ("argmax", "count") else v
+            pairs = a[:, :, 6:].reshape(a.shape[0], a.shape[1], lv.size, 2)
+            d["lo"] = np.ascontiguousarray(pairs[..., 0].transpose(0, 2, 1))
+            d["hi"] = np.ascontiguousarray(pairs[..., 1].transpose(0, 2, 1))
+            d["value"] = quantile_value(d["lo"], d["hi"], g) if lv.size else d["lo"].copy()
+            out[name] = d
+        return np.arange(n) * self.Ts, out
+
     def _score_step(self, y):
         """The instant's indices (enable_scores): one launch on the step's stream."""
         tgt = 0
@@ -463,6 +506,8 @@ class ClosedLoop:
         self.t_seg, self.seg_step = 0.0, 0   # integrate_const's start time and step count
         if self._scores:
             self.ctx.score_reset()
+        if self._envelope:
+            self.ctx.envelope_reset()
 
     def step(self, trace: bool = False, predict: bool = False, certify=None):
         """One sampling instant: returns (t, y) of the instant; the plant has
@@ -507,6 +552,8 @@ class ClosedLoop:
                                                  self.torch_ptr(self.u_ctrl)), "cmpc_accumulate_moves")
         if self._scores:
             self._score_step(y)
+        if self._envelope:
+            self.ctx.envelope_step(y.data_ptr(), self.u_ctrl.data_ptr())
         # SetInput(u) through the delay line, then the plant over [t, t + Ts];
         # at the end of a segment's Integrate call: SetOffset and a new call
         self._disturb()

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "dispatch.h"
+#include "ensemble_select.h"
 #include "noise_body.h"
 
 namespace {
@@ -258,6 +259,18 @@ struct cmpc_ctx {
       if (p) (void)hipFree(p);
     }
   } score_ens_work;
+  // exact quantiles of the score record (cmpc_score_quantiles): the work
+  // buffer, allocated by the first call.  The envelope (cmpc_envelope_*):
+  // everything is allocated by cmpc_envelope_enable and released by
+  // cmpc_envelope_disable or with the context; env_rows are the rows in force
+  // (own or bound).  (After score_ens_work, for the same reason.)
+  DeviceBuf quant_work;
+  bool env_on = false;
+  int env_nout = 0, env_tcap = 0;
+  int64_t env_k = 0;  // steps since the last reset
+  QuantileRanks env_ranks{};
+  DeviceBuf env_thr, env_mom_work, env_quant_work, env_own;
+  double* env_rows = nullptr;
 };
 
 namespace {
@@ -2933,6 +2946,235 @@ int cmpc_score_ensemble(cmpc_ctx* c, const double* thresholds, double* out) {
   HIP_TRY(hipMemcpyAsync(out, work, sizeof(double) * (size_t)len * S * kScoreEnsembleStats, hipMemcpyDeviceToHost,
                          c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// Exact ensemble quantiles and the envelope (include/cmpc.h, ensemble_select.h,
+// ensemble_quantiles.hip).
+static int quantile_levels_check(const char* who, int n_levels, int n_min, const double* levels) {
+  if (n_levels < n_min || n_levels > CMPC_QUANTILE_MAX_LEVELS)
+    return fail(std::string(who) + ": n_levels must be inside [" + std::to_string(n_min) + ", " +
+                std::to_string(CMPC_QUANTILE_MAX_LEVELS) + "]");
+  if (n_levels > 0 && !levels) return fail(std::string(who) + ": null levels");
+  for (int l = 0; l < n_levels; ++l)
+    if (!(levels[l] >= 0.0 && levels[l] <= 1.0))
+      return fail(std::string(who) + ": level " + std::to_string(l) + " must be inside [0, 1]");
+  return 0;
+}
+
+static QuantileRanks quantile_ranks(int B, int n_levels, const double* levels, double* g) {
+  QuantileRanks R{};
+  R.n = n_levels;
+  for (int l = 0; l < n_levels; ++l) {
+    double gl;
+    cmpc_select_rank(B, levels[l], &R.k_lo[l], &R.k_hi[l], &gl);
+    if (g) g[l] = gl;
+  }
+  return R;
+}
+
+int cmpc_quantile_check(int B, int n_levels, const double* levels) {
+  if (B < 1) return fail("cmpc_quantile: B must be >= 1");
+  return quantile_levels_check("cmpc_quantile", n_levels, 1, levels);
+}
+
+int cmpc_quantile_rank(int B, double level, int32_t* k_lo, int32_t* k_hi, double* g) {
+  if (!k_lo || !k_hi || !g) return fail("cmpc_quantile_rank: null argument");
+  if (cmpc_quantile_check(B, 1, &level)) return -1;
+  uint32_t lo, hi;
+  cmpc_select_rank(B, level, &lo, &hi, g);
+  *k_lo = (int32_t)lo;
+  *k_hi = (int32_t)hi;
+  return 0;
+}
+
+double cmpc_quantile_value(double x_lo, double x_hi, double g) { return cmpc_select_interpolate(x_lo, x_hi, g); }
+
+int cmpc_quantiles_host(const double* x, int len, int B, int S, int n_levels, const double* levels, double* out) {
+  if (!x || !out) return fail("cmpc_quantiles_host: null argument");
+  if (cmpc_quantile_check(B, n_levels, levels)) return -1;
+  if (len < 1 || S < 1) return fail("cmpc_quantiles_host: len and S must be >= 1");
+  const QuantileRanks R = quantile_ranks(B, n_levels, levels, nullptr);
+  for (int f = 0; f < len; ++f)
+    for (int s = 0; s < S; ++s)
+      cmpc_select_row_host(x + (size_t)f * B * S + s, (size_t)S, B, n_levels, R.k_lo, R.k_hi,
+                           out + ((size_t)f * S + s) * n_levels * 3);
+  return 0;
+}
+
+int cmpc_score_quantiles(cmpc_ctx* c, int n_levels, const double* levels, double* out) {
+  if (!c || !out) return fail("cmpc_score_quantiles: null argument");
+  if (!c->score_on) return fail("cmpc_score_quantiles: scoring is not enabled (cmpc_score_enable)");
+  if (cmpc_quantile_check(c->d.B, n_levels, levels)) return -1;
+  const int len = cmpc_score_fields(c->d.ny, c->d.nu).len, S = c->d.S, B = c->d.B;
+  if ((size_t)len * S > 65535) return fail("cmpc_score_quantiles: more rows than one launch covers");
+  const int rows = len * S;
+  HIP_TRY(hipSetDevice(c->device));
+  if (!c->quant_work.p)
+    HIP_TRY(hipMalloc(&c->quant_work.p, cmpc_quantile_work_bytes(rows, B, CMPC_QUANTILE_MAX_LEVELS)));
+  void* work = c->quant_work.p;
+  EnsRowMap M{};
+  M.p0 = c->score_rec;
+  M.fstride0 = (int64_t)B * S;
+  M.rows0 = rows;
+  M.S0 = S;
+  const QuantileRanks R = quantile_ranks(B, n_levels, levels, nullptr);
+  const QuantileOut O{static_cast<double*>(work), (int64_t)n_levels * 3, 3};
+  if (cmpc_launch_quantiles(M, B, R, O, work, c->stream)) return plan_mismatch("score quantiles");
+  if (check_launch("quantile kernels")) return -1;
+  HIP_TRY(hipMemcpyAsync(out, O.out, sizeof(double) * (size_t)rows * n_levels * 3, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+static int envelope_width(int n_levels) { return kScoreEnsembleStats + 2 * n_levels; }
+
+int cmpc_envelope_check(const cmpc_dims* dims, int n_outputs, int t_cap, int n_levels, const double* levels,
+                        const double* thresholds) {
+  cmpc_layout L;
+  if (!dims) return fail("cmpc_envelope_enable: null argument");
+  if (layout_of(dims, &L)) return -1;
+  if (n_outputs < 1) return fail("cmpc_envelope_enable: n_outputs must be >= 1");
+  if (t_cap < 1) return fail("cmpc_envelope_enable: t_cap must be >= 1");
+  if (quantile_levels_check("cmpc_envelope_enable", n_levels, 0, levels)) return -1;
+  if ((int64_t)n_outputs + dims->nu_tot > 65535)
+    return fail("cmpc_envelope_enable: more channels than one launch covers");
+  for (int ch = 0; thresholds && ch < n_outputs + dims->nu_tot; ++ch)
+    if (std::isnan(thresholds[ch]))
+      return fail("cmpc_envelope_enable: threshold of channel " + std::to_string(ch) + " is not a number");
+  return 0;
+}
+
+int cmpc_envelope_len(const cmpc_dims* dims, int n_outputs, int n_levels) {
+  cmpc_layout L;
+  if (!dims) return fail("cmpc_envelope_len: null argument");
+  if (layout_of(dims, &L)) return -1;
+  if (n_outputs < 1 || n_levels < 0 || n_levels > CMPC_QUANTILE_MAX_LEVELS ||
+      (int64_t)n_outputs + dims->nu_tot > 65535)
+    return fail("cmpc_envelope_len: n_outputs or n_levels outside the limits");
+  return (n_outputs + dims->nu_tot) * envelope_width(n_levels);
+}
+
+static size_t envelope_row_len(const cmpc_ctx* c) {
+  return (size_t)(c->env_nout + c->d.nu_tot) * envelope_width(c->env_ranks.n);
+}
+
+static void envelope_free(cmpc_ctx* c) {
+  for (auto* b : {&c->env_thr, &c->env_mom_work, &c->env_quant_work, &c->env_own}) {
+    if (b->p) (void)hipFree(b->p);
+    b->p = nullptr;
+  }
+  c->env_rows = nullptr;
+  c->env_on = false;
+  c->env_k = 0;
+}
+
+int cmpc_envelope_disable(cmpc_ctx* c) {
+  if (!c) return fail("null context");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  envelope_free(c);
+  return 0;
+}
+
+int cmpc_envelope_enable(cmpc_ctx* c, int n_outputs, int t_cap, int n_levels, const double* levels,
+                         const double* thresholds) {
+  if (!c) return fail("null context");
+  if (cmpc_envelope_check(&c->d, n_outputs, t_cap, n_levels, levels, thresholds)) return -1;
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  envelope_free(c);
+  const int chans = n_outputs + c->d.nu_tot, B = c->d.B;
+  c->env_nout = n_outputs;
+  c->env_tcap = t_cap;
+  c->env_ranks = quantile_ranks(B, n_levels, levels, nullptr);
+  const size_t rows = sizeof(double) * (size_t)t_cap * envelope_row_len(c);
+  HIP_TRY(hipMalloc(&c->env_own.p, rows));
+  HIP_TRY(hipMemsetAsync(c->env_own.p, 0, rows, c->stream));
+  HIP_TRY(hipMalloc(&c->env_mom_work.p, cmpc_envelope_moments_bytes(chans)));
+  if (thresholds) {
+    HIP_TRY(hipMalloc(&c->env_thr.p, sizeof(double) * chans));
+    HIP_TRY(hipMemcpyAsync(c->env_thr.p, thresholds, sizeof(double) * chans, hipMemcpyHostToDevice, c->stream));
+  }
+  if (n_levels > 0) {
+    // (a step without u_control covers n_outputs rows, with its own block count)
+    const size_t bytes = std::max(cmpc_quantile_work_bytes(chans, B, n_levels),
+                                  cmpc_quantile_work_bytes(n_outputs, B, n_levels));
+    HIP_TRY(hipMalloc(&c->env_quant_work.p, bytes));
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->env_rows = static_cast<double*>(c->env_own.p);
+  c->env_k = 0;
+  c->env_on = true;
+  return 0;
+}
+
+int cmpc_envelope_reset(cmpc_ctx* c) {
+  if (!c) return fail("null context");
+  if (!c->env_on) return fail("cmpc_envelope_reset: no envelope is enabled (cmpc_envelope_enable)");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipMemsetAsync(c->env_own.p, 0, sizeof(double) * (size_t)c->env_tcap * envelope_row_len(c), c->stream));
+  c->env_k = 0;
+  return 0;
+}
+
+int cmpc_envelope_bind(cmpc_ctx* c, double* rows_device) {
+  if (!c) return fail("null context");
+  if (!c->env_on) return fail("cmpc_envelope_bind: no envelope is enabled (cmpc_envelope_enable)");
+  if (rows_device) {
+    const size_t bytes = sizeof(double) * (size_t)c->env_tcap * envelope_row_len(c);
+    if (!device_ptr_ok(c, rows_device, bytes)) {
+      (void)hipGetLastError();  // a failed pointer query is not a later launch's error
+      return fail("cmpc_envelope_bind: not a device allocation of t_cap * cmpc_envelope_len doubles on the "
+                  "context's device");
+    }
+    if (reinterpret_cast<uintptr_t>(rows_device) % 8) return fail("cmpc_envelope_bind: misaligned array");
+  }
+  c->env_rows = rows_device ? rows_device : static_cast<double*>(c->env_own.p);
+  return 0;
+}
+
+int cmpc_envelope_step(cmpc_ctx* c, const double* y, const double* u_control) {
+  if (!c) return fail("null context");
+  if (!c->env_on) return fail("cmpc_envelope_step: no envelope is enabled (cmpc_envelope_enable)");
+  if (!y) return fail("cmpc_envelope_step: null y");
+  if (c->env_k >= c->env_tcap) {  // dropped, as the capture drops its steps
+    if (c->env_k < INT32_MAX) c->env_k++;
+    return 0;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  const int W = envelope_width(c->env_ranks.n);
+  EnsRowMap M{};
+  M.p0 = y;
+  M.rows0 = M.S0 = c->env_nout;
+  M.fstride0 = 0;
+  if (u_control) {
+    M.p1 = u_control;
+    M.rows1 = M.S1 = c->d.nu_tot;
+  }
+  double* row = c->env_rows + (size_t)c->env_k * envelope_row_len(c);
+  if (cmpc_launch_envelope_moments(M, c->d.B, static_cast<const double*>(c->env_thr.p), row, W, c->env_mom_work.p,
+                                   c->stream))
+    return plan_mismatch("envelope statistics");
+  if (c->env_ranks.n > 0) {
+    const QuantileOut O{row + kScoreEnsembleStats, W, 2};
+    if (cmpc_launch_quantiles(M, c->d.B, c->env_ranks, O, c->env_quant_work.p, c->stream))
+      return plan_mismatch("envelope quantiles");
+  }
+  if (check_launch("envelope kernels")) return -1;
+  c->env_k++;
+  return 0;
+}
+
+int cmpc_envelope_download(cmpc_ctx* c, double* rows, int32_t* n_rows) {
+  if (!c) return fail("null context");
+  if (!c->env_on) return fail("cmpc_envelope_download: no envelope is enabled (cmpc_envelope_enable)");
+  HIP_TRY(hipSetDevice(c->device));
+  if (rows)
+    HIP_TRY(hipMemcpyAsync(rows, c->env_rows, sizeof(double) * (size_t)c->env_tcap * envelope_row_len(c),
+                           hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (n_rows) *n_rows = (int32_t)std::min<int64_t>(c->env_k, c->env_tcap);
   return 0;
 }
 

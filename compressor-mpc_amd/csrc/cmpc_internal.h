@@ -406,6 +406,47 @@ double* cmpc_score_ensemble_thresholds(void* work, int len, int S);
 // three launches: partials per block, centred squares per block, a wave per row over both
 int cmpc_launch_score_ensemble(const double* rec, int len, int B, int S, bool has_thr, void* work, void* stream);
 
+// Exact ensemble quantiles and the per-step envelope (ensemble_quantiles.hip,
+// cmpc_score_quantiles, cmpc_envelope_step); the selection
+// arithmetic is ensemble_select.h's, shared with the host entry points.
+// The rows reduced over the B scenarios, in two segments: row r < rows0 is
+// (f, s) = (r / S0, r mod S0) of a (len, B, S0) array, x_b = p0[f * fstride0 +
+// b * S0 + s] (the score record: fstride0 = B * S0; a scenario-major (B x C)
+// array: rows0 = S0 = C); row rows0 + c is column c of the scenario-major
+// (B x S1) array p1.
+struct EnsRowMap {
+  const double *p0, *p1;
+  int64_t fstride0;
+  int rows0, S0, rows1, S1;
+};
+// the ranks of a call's levels, computed on the host (cmpc_select_rank)
+struct QuantileRanks {
+  uint32_t k_lo[CMPC_QUANTILE_MAX_LEVELS], k_hi[CMPC_QUANTILE_MAX_LEVELS];
+  int n;
+};
+// where the results go: row r's at out + r * row_stride; level l's x_lo, x_hi
+// (and, with lvl_stride 3, arg) at + l * lvl_stride
+struct QuantileOut {
+  double* out;
+  int64_t row_stride;
+  int lvl_stride;
+};
+// blocks per row a call launches: a function of (rows, B) alone
+int cmpc_quantile_blocks(int rows, int B);
+// bytes of the work buffer for up to n_levels levels.  Its head is room for
+// rows * n_levels * 3 doubles, for a caller that wants the results there.
+size_t cmpc_quantile_work_bytes(int rows, int B, int n_levels);
+// 18 launches (two per digit, two for the last pass), nothing else; -1: an
+// argument outside the limits
+int cmpc_launch_quantiles(const EnsRowMap& M, int B, const QuantileRanks& R, const QuantileOut& O, void* work,
+                          void* stream);
+// The six statistics of cmpc_score_ensemble over an EnsRowMap's rows, row r's
+// at out + r * row_stride, the count against thr[r] (device, one per row, or
+// null: 0).  Three launches; `work` holds cmpc_envelope_moments_bytes(rows).
+size_t cmpc_envelope_moments_bytes(int rows);
+int cmpc_launch_envelope_moments(const EnsRowMap& M, int B, const double* thr, double* out, int64_t row_stride,
+                                 void* work, void* stream);
+
 // Standalone batched solver (parity / KKT tests).  G (nqp * n * nvo) and d
 // (nqp * nvo) non-null: the Jacobi iteration's map-form solve with g = f + G d
 // (cmpc_qp_solve_batch_map); g is f then.

@@ -748,6 +748,95 @@ int cmpc_certify_summary(cmpc_ctx* ctx, double tol, cmpc_certify_summary_t* out)
  *   and for a threshold that is not a number. */
 int cmpc_score_ensemble(cmpc_ctx* ctx, const double* thresholds, double* out);
 
+/* Exact ensemble quantiles and per-step envelopes (ensemble_select.h,
+ * ensemble_quantiles.hip): the median, P95, P99 of a score
+ * row, and per sampling instant the spread of every output and input over the
+ * ensemble (a fan chart), without the per-scenario data leaving the device.
+ *
+ *   order   values are ordered as  -inf < negatives < -0 < +0 < positives <
+ *           +inf < NaN  (a double's bits u as the key u | 2^63 with the sign
+ *           clear, ~u with it set; every NaN the largest key, returned as the
+ *           one quiet NaN 0x7ff8000000000000): np.sort's order
+ *   rank    for B values and a level q in [0, 1]: h = q (double)(B - 1) (one
+ *           product), k_lo = floor(h), g = h - k_lo (exact), k_hi = k_lo + 1
+ *           where g > 0, else k_lo
+ *   result  per (row, level) three doubles: x_lo and x_hi, the values at
+ *           sorted positions k_lo and k_hi, and arg, the lowest scenario b
+ *           whose key is x_lo's (the scenario to replay as "the P95 scenario")
+ *   value   cmpc_quantile_value(x_lo, x_hi, g) = x_lo where x_lo == x_hi; else
+ *           with d = x_hi - x_lo: x_lo + d g for g < 0.5, x_hi - d (1 - g)
+ *           otherwise (products and sums separate).  On finite data this is
+ *           numpy's quantile (linear method) bit for bit; between a finite
+ *           value and an infinity it is the infinity where numpy gives NaN
+ * x_lo, x_hi and arg equal a sort's bit for bit and do not depend on the
+ * launch shape: the selection is integer counting (an MSB-first radix
+ * selection with 8-bit digits), with no floating-point atomics.
+ *
+ * Host only (no device is touched); refused (-1, cmpc_last_error names the
+ * cause): B < 1, n_levels outside [1, CMPC_QUANTILE_MAX_LEVELS], a level
+ * outside [0, 1] or not a number, a NULL pointer.
+ * cmpc_quantile_check: the argument check of the others.
+ * cmpc_quantile_rank: the rank rule for one level.
+ * cmpc_quantile_value: the value rule (no refusals).
+ * cmpc_quantiles_host: the same selection on host memory.  x is a (len, B, S)
+ *   array, row (f, s) holding x_b = x[f*B*S + b*S + s] (a scenario-major
+ *   (B x C) array is len = 1, S = C); out holds len*S*n_levels*3 doubles, row
+ *   (f, s), level l at ((f*S + s)*n_levels + l)*3.
+ *
+ * cmpc_score_quantiles: the same for every row of the score record in force
+ *   (own or bound, cmpc_score_bind), len = cmpc_score_len, on the device: 18
+ *   launches whatever the arguments (two per digit, two for the last pass),
+ *   one copy and one stream synchronisation.  levels: n_levels host doubles; out:
+ *   len*S*n_levels*3 host doubles in cmpc_quantiles_host's layout.  It reads
+ *   the record and changes nothing but its own work buffer, allocated by the
+ *   first call and released with the context.  Refused before
+ *   cmpc_score_enable and as cmpc_quantile_check refuses.
+ *
+ * The envelope: per sampling instant k and channel c (the n_outputs plant
+ * outputs, then the nu_tot control inputs), over the B scenarios, W = 6 +
+ * 2 n_levels doubles at rows[(k*C + c)*W], C = n_outputs + nu_tot:
+ *   0..5  cmpc_score_ensemble's six statistics in its order, the count
+ *         against thresholds[c] (0 with thresholds NULL)
+ *   6 + 2l, 7 + 2l   x_lo, x_hi of level l
+ * cmpc_envelope_check: host only, the argument check of cmpc_envelope_enable.
+ *   Refused: n_outputs < 1, t_cap < 1, n_levels outside [0,
+ *   CMPC_QUANTILE_MAX_LEVELS] (0: the statistics only), a level outside [0, 1]
+ *   or not a number, NULL levels with n_levels > 0, a threshold that is not a
+ *   number, more than 65535 channels.
+ * cmpc_envelope_len: host only, C*W, the doubles per step row.
+ * cmpc_envelope_enable: allocates the rows (t_cap of them, zero) and the work
+ *   buffers, uploads the thresholds (n_outputs + nu_tot host doubles or NULL)
+ *   and starts at k = 0.  A context that never calls it allocates and launches
+ *   nothing for the envelope.
+ * cmpc_envelope_step: y_device (B x n_outputs) and u_control_device (B x
+ *   nu_tot, or NULL: its channels stay zero) are scenario-major device arrays.
+ *   Launches only, on the context's stream (3 for the statistics, 18 more with
+ *   n_levels > 0): no copy, no synchronisation; row k of the rows in force is
+ *   written directly.  Steps k >= t_cap are dropped, not wrapped.  Refused
+ *   before cmpc_envelope_enable and for a NULL y.
+ * cmpc_envelope_reset: k = 0 (own rows are zeroed; bound ones are the caller's).
+ * cmpc_envelope_bind: keep the rows in a device buffer of t_cap *
+ *   cmpc_envelope_len doubles (NULL: the context's own).
+ * cmpc_envelope_download: t_cap * cmpc_envelope_len doubles (rows may be NULL)
+ *   and the number of rows recorded, min(k, t_cap); synchronises the stream.
+ * cmpc_envelope_disable: releases everything the envelope allocated. */
+#define CMPC_QUANTILE_MAX_LEVELS 8
+int cmpc_quantile_check(int B, int n_levels, const double* levels);
+int cmpc_quantile_rank(int B, double level, int32_t* k_lo, int32_t* k_hi, double* g);
+double cmpc_quantile_value(double x_lo, double x_hi, double g);
+int cmpc_quantiles_host(const double* x, int len, int B, int S, int n_levels, const double* levels, double* out);
+int cmpc_score_quantiles(cmpc_ctx* ctx, int n_levels, const double* levels, double* out);
+int cmpc_envelope_check(const cmpc_dims* dims, int n_outputs, int t_cap, int n_levels, const double* levels,
+                        const double* thresholds);
+int cmpc_envelope_len(const cmpc_dims* dims, int n_outputs, int n_levels);
+int cmpc_envelope_enable(cmpc_ctx* ctx, int n_outputs, int t_cap, int n_levels, const double* levels,
+                         const double* thresholds);
+int cmpc_envelope_step(cmpc_ctx* ctx, const double* y_device, const double* u_control_device);
+int cmpc_envelope_reset(cmpc_ctx* ctx);
+int cmpc_envelope_bind(cmpc_ctx* ctx, double* rows_device);
+int cmpc_envelope_download(cmpc_ctx* ctx, double* rows, int32_t* n_rows);
+int cmpc_envelope_disable(cmpc_ctx* ctx);
+
 /* Seeded per-scenario noise and disturbances (noise_body.h, noise.hip,
  * DESIGN.md §3.17): normal draws that are a pure function of (seed, stream,
  * global scenario, step, channel), so a run is reproducible from its seed and
