@@ -27,6 +27,9 @@ from ._abi import (CMPC_BUILD_AUTO, CMPC_BUILD_ROWS, CMPC_BUILD_SPLIT, CMPC_BUIL
                    check, dptr, iptr, load_library, uptr)
 from .configs import ControllerConfig, SetupFile, reference_config, reference_observer_gain, reference_setup
 from .problem import ControllerArrays, controller_arrays, plant_input_from_plans
+from ._abi import (CMPC_EQ_OK, CMPC_EQ_NO_CONVERGENCE, CMPC_EQ_NONFINITE, CMPC_EQ_SINGULAR,  # noqa: F401
+                   CMPC_EQ_SKIPPED)
+from .sim import plant_derivative, plant_equilibrium  # noqa: F401
 
 __all__ = ["Context", "ControllerConfig", "SetupFile", "reference_config", "reference_setup",
            "reference_observer_gain", "controller_arrays",
@@ -41,7 +44,9 @@ __all__ = ["Context", "ControllerConfig", "SetupFile", "reference_config", "refe
            "noise_key", "noise_check", "noise_check_params", "noise_uniforms_host", "noise_step_host",
            "noise_uniforms", "noise_step", "noise_uniforms_ptr", "noise_step_ptr",
            "CMPC_NOISE_STREAM_MEASUREMENT", "CMPC_NOISE_STREAM_INPUT",
-           "quantile_check", "quantile_rank", "quantile_value", "quantiles_host", "envelope_check", "envelope_len"]
+           "quantile_check", "quantile_rank", "quantile_value", "quantiles_host", "envelope_check", "envelope_len",
+           "plant_derivative", "plant_equilibrium", "CMPC_EQ_OK", "CMPC_EQ_NO_CONVERGENCE", "CMPC_EQ_NONFINITE",
+           "CMPC_EQ_SINGULAR", "CMPC_EQ_SKIPPED"]
 
 
 def layout_of(dims: CmpcDims) -> CmpcLayout:

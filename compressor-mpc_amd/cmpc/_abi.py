@@ -165,7 +165,18 @@ EXPORTS = (
     "cmpc_quantile_check", "cmpc_quantile_rank", "cmpc_quantiles_host", "cmpc_score_quantiles",
     "cmpc_envelope_check", "cmpc_envelope_len", "cmpc_envelope_enable", "cmpc_envelope_step",
     "cmpc_envelope_reset", "cmpc_envelope_bind", "cmpc_envelope_download", "cmpc_envelope_disable",
+    "cmpc_plant_derivative", "cmpc_plant_equilibrium_host", "cmpc_sim_equilibrium",
+    "cmpc_sim_equilibrium_download", "cmpc_sim_equilibrium_status", "cmpc_sim_equilibrium_iters",
+    "cmpc_sim_equilibrium_resid",
 )
+
+# per-scenario statuses of the equilibrium solve (include/cmpc.h)
+CMPC_EQ_OK = 0
+CMPC_EQ_NO_CONVERGENCE = 1
+CMPC_EQ_NONFINITE = 2
+CMPC_EQ_SINGULAR = 3
+CMPC_EQ_SKIPPED = 4
+CMPC_EQ_MAX_ITER = 64
 
 # the fields of a slot's score record, in the record's order (cmpc_score_field
 # gives each one's rows; include/cmpc.h has the table)
@@ -400,6 +411,14 @@ def load_library(path: str = LIB_PATH):
         "cmpc_envelope_bind": ([c_void, c_void], ctypes.c_int),
         "cmpc_envelope_download": ([c_void, P(dbl), P(i32)], ctypes.c_int),
         "cmpc_envelope_disable": ([c_void], ctypes.c_int),
+        "cmpc_plant_derivative": ([ctypes.c_int, dbl, dbl, P(dbl), P(dbl), P(dbl)], ctypes.c_int),
+        "cmpc_plant_equilibrium_host": ([ctypes.c_int, ctypes.c_int, P(dbl), P(dbl), P(dbl), ctypes.c_int, dbl,
+                                         P(i32), P(i32), P(dbl)], ctypes.c_int),
+        "cmpc_sim_equilibrium": ([c_void, ctypes.c_int, dbl], ctypes.c_int),
+        "cmpc_sim_equilibrium_download": ([c_void, P(i32), P(i32), P(dbl)], ctypes.c_int),
+        "cmpc_sim_equilibrium_status": ([c_void], c_void),
+        "cmpc_sim_equilibrium_iters": ([c_void], c_void),
+        "cmpc_sim_equilibrium_resid": ([c_void], c_void),
         "cmpc_qp_solve_batch": ([ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(dbl),
                                  P(dbl), P(dbl), P(dbl), P(dbl), P(dbl), P(u32), ctypes.c_int,
                                  P(dbl), P(i32), P(i32), P(u32), P(ctypes.c_uint8), P(i32)],

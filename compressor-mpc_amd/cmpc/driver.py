@@ -34,7 +34,7 @@ import numpy as np
 
 from . import CMPC_TRACE, Context, scenario_limits, scenario_reference_offsets
 from .configs import ControllerConfig
-from .sim import REF_CONTROL_INDEX, REF_DELAYS, REF_EPS, REF_TS, PlantSimulator
+from .sim import EQ_MAX_ITER, EQ_TOL, REF_CONTROL_INDEX, REF_DELAYS, REF_EPS, REF_TS, PlantSimulator
 
 
 def _fmt(v: float) -> str:
@@ -483,6 +483,24 @@ class ClosedLoop:
         rows = rows[:n]
         return (np.arange(n) * self.Ts, np.ascontiguousarray(rows[:, :, :no]),
                 np.ascontiguousarray(rows[:, :, no:no + nu]), np.ascontiguousarray(rows[:, :, no + nu:]))
+
+    def trim(self, max_iter: int = EQ_MAX_ITER, tol: float = EQ_TOL):
+        """Start every scenario at its own plant equilibrium (call before
+        initialize): the plant is reset to x0 and u_offset, the plant's
+        pressures are put in force (row 0 of a pressure schedule, the
+        per-scenario array, or the scalars), PlantSimulator.equilibrium solves
+        f(x, u_offset, p) = 0 from x0 on the device, and x0 becomes the
+        simulator's state: the equilibrium where the scenario's status is
+        CMPC_EQ_OK, its given x0 elsewhere.  Returns (status, iters, resid),
+        (B,) host arrays.  initialize then starts plant and observers there
+        (y_old = y(x0)); self.sim.output() gives the outputs at rest, for
+        setpoints relative to them."""
+        self.sim.reset(self.x0, self.u_offset, self.Ts)
+        self.k = 0
+        self._pressure_rows()
+        out = self.sim.equilibrium(max_iter, tol)
+        self.x0 = self.torch.from_numpy(self.sim.download()[0]).to(self.dev)
+        return out
 
     def initialize(self, dx_init=None):
         """SimulationSystem(x0, u_offset) + NerveCenter::Initialize(x0, 0,

@@ -8,12 +8,54 @@ import ctypes
 
 import numpy as np
 
-from ._abi import check, load_library
+from ._abi import check, dptr, iptr, load_library
 
 REF_DELAYS = (0, 40, 0, 40)          # Delays of both plants (control-input order)
 REF_CONTROL_INDEX = (0, 3, 4, 7)     # ControlInputIndex: plant input of each control input
 REF_TS = 0.05                        # sampling time of results/*.dat
 REF_EPS = 1e-6                       # Integrate's max_rel_error / max_abs_error
+EQ_MAX_ITER = 20                     # equilibrium solve: Newton steps allowed and the
+EQ_TOL = 1e-12                       # bound on max|f|
+
+
+def _plant_sizes(lib, plant: int):
+    ns, ni = ctypes.c_int(), ctypes.c_int()
+    check(lib.cmpc_plant_dims(plant, ctypes.byref(ns), ctypes.byref(ni), None, None), "cmpc_plant_dims")
+    return ns.value, ni.value
+
+
+def plant_derivative(plant: int, x, u_full, p_in: float = 1.0, p_out: float = 1.0) -> np.ndarray:
+    """dx = f(x, u_full) of the plant at the boundary pressures (host)."""
+    lib = load_library()
+    ns, ni = _plant_sizes(lib, plant)
+    x = np.ascontiguousarray(x, np.float64)
+    u = np.ascontiguousarray(u_full, np.float64)
+    if x.shape != (ns,) or u.shape != (ni,):
+        raise ValueError(f"x must be ({ns},) and u_full ({ni},), got {x.shape} and {u.shape}")
+    dx = np.zeros(ns)
+    check(lib.cmpc_plant_derivative(plant, p_in, p_out, dptr(x), dptr(u), dptr(dx)), "cmpc_plant_derivative")
+    return dx
+
+
+def plant_equilibrium(plant: int, pressures, u_full, x0, max_iter: int = EQ_MAX_ITER, tol: float = EQ_TOL):
+    """The plant's equilibrium for B scenarios on the host (no device):
+    pressures (B, 2) of [p_in, p_out], u_full (B, n_inputs), x0 (B, ns) the
+    Newton start.  Returns (x, status, iters, resid): x (B, ns) is the
+    equilibrium where status is CMPC_EQ_OK and x0's row elsewhere; the
+    arithmetic is PlantSimulator.equilibrium's, bit for bit."""
+    lib = load_library()
+    ns, ni = _plant_sizes(lib, plant)
+    x = np.array(x0, dtype=np.float64, order="C")
+    B = x.shape[0] if x.ndim == 2 else 0
+    p = np.ascontiguousarray(pressures, np.float64)
+    u = np.ascontiguousarray(u_full, np.float64)
+    if B < 1 or x.shape != (B, ns) or p.shape != (B, 2) or u.shape != (B, ni):
+        raise ValueError(f"x0 must be (B, {ns}), pressures (B, 2) and u_full (B, {ni}), "
+                         f"got {x.shape}, {p.shape} and {u.shape}")
+    status, iters, resid = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B)
+    check(lib.cmpc_plant_equilibrium_host(plant, B, dptr(p), dptr(u), dptr(x), max_iter, tol, iptr(status),
+                                          iptr(iters), dptr(resid)), "cmpc_plant_equilibrium_host")
+    return x, status, iters, resid
 
 
 class PlantSimulator:
@@ -132,6 +174,18 @@ class PlantSimulator:
 
     def integrate(self, t: float, t_end: float, eps_abs: float = REF_EPS, eps_rel: float = REF_EPS):
         check(self.lib.cmpc_sim_integrate(self._h, t, t_end, eps_abs, eps_rel), "cmpc_sim_integrate")
+
+    def equilibrium(self, max_iter: int = EQ_MAX_ITER, tol: float = EQ_TOL):
+        """Move every scenario to its plant equilibrium f(x, u, p) = 0 by
+        Newton's method from its current state, at its current plant input and
+        the pressures in force (one launch; the step sizes and the delay lines
+        stay).  Returns (status, iters, resid), (B,) host arrays: the state of
+        a scenario whose status is not CMPC_EQ_OK is left as it was."""
+        check(self.lib.cmpc_sim_equilibrium(self._h, max_iter, tol), "cmpc_sim_equilibrium")
+        status, iters, resid = np.zeros(self.B, np.int32), np.zeros(self.B, np.int32), np.zeros(self.B)
+        check(self.lib.cmpc_sim_equilibrium_download(self._h, iptr(status), iptr(iters), dptr(resid)),
+              "cmpc_sim_equilibrium_download")
+        return status, iters, resid
 
     def output(self, out=None):
         """GetOutput into out (B, n_outputs) (default: self.y)."""

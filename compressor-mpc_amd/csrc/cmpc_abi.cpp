@@ -21,6 +21,7 @@
 
 #include "dispatch.h"
 #include "ensemble_select.h"
+#include "equilibrium_body.h"
 #include "noise_body.h"
 
 namespace {
@@ -1552,6 +1553,9 @@ struct cmpc_sim {
   // (cmpc_sim_set_pressures[_host], allocated on first use) or a bound array
   const double* pr = nullptr;
   double* own_pr = nullptr;
+  // results of the last cmpc_sim_equilibrium (B each, allocated on first use)
+  int32_t *eq_status = nullptr, *eq_iters = nullptr;
+  double* eq_resid = nullptr;
   PinnedIO pin_in, pin_out;  // host-array calls: page-locked staging
 };
 
@@ -1614,7 +1618,8 @@ int cmpc_sim_destroy(cmpc_sim* m) {
   if (m->stream) (void)hipStreamSynchronize(m->stream);
   pinned_free(m->pin_in);
   pinned_free(m->pin_out);
-  void* bufs[] = {m->x, m->dt, m->u_full, m->u_offset, m->ring, m->scratch, m->stage, m->status, m->own_pr};
+  void* bufs[] = {m->x, m->dt, m->u_full, m->u_offset, m->ring, m->scratch, m->stage, m->status, m->own_pr,
+                  m->eq_status, m->eq_iters, m->eq_resid};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (m->own_stream && m->stream) (void)hipStreamDestroy(m->stream);
@@ -1830,6 +1835,82 @@ int cmpc_sim_get_pressures(cmpc_sim* m, double* pressures) {
   HIP_TRY(hipStreamSynchronize(m->stream));
   return 0;
 }
+
+// Plant equilibrium (include/cmpc.h, equilibrium_body.h, equilibrium.hip)
+static int equilibrium_check(const char* who, int max_iter, double tol) {
+  if (max_iter < 0 || max_iter > CMPC_EQ_MAX_ITER)
+    return fail(std::string(who) + ": max_iter must be in [0, " + std::to_string(CMPC_EQ_MAX_ITER) + "]");
+  if (!std::isfinite(tol) || !(tol > 0)) return fail(std::string(who) + ": tol must be finite and positive");
+  return 0;
+}
+
+int cmpc_plant_equilibrium_host(int plant, int B, const double* pressures, const double* u_full, double* x,
+                                int max_iter, double tol, int32_t* status, int32_t* iters, double* resid) {
+  int ns = 0, ni = 0, no = 0, nci = 0;
+  if (cmpc_plant_dims(plant, &ns, &ni, &no, &nci)) return fail("cmpc_plant_equilibrium_host: unknown plant");
+  if (B < 1) return fail("cmpc_plant_equilibrium_host: B must be >= 1");
+  if (!pressures || !u_full || !x || !status || !iters || !resid)
+    return fail("cmpc_plant_equilibrium_host: null argument");
+  if (equilibrium_check("cmpc_plant_equilibrium_host", max_iter, tol)) return -1;
+  for (size_t b = 0; b < (size_t)B; ++b) {
+    const double p_in = pressures[2 * b], p_out = pressures[2 * b + 1];
+    status[b] = plant == CMPC_PLANT_PARALLEL
+                    ? cmpc_eq::eq_solve<CMPC_PLANT_PARALLEL>(p_in, p_out, u_full + b * ni, x + b * ns, max_iter, tol,
+                                                             iters + b, resid + b)
+                    : cmpc_eq::eq_solve<CMPC_PLANT_SERIAL>(p_in, p_out, u_full + b * ni, x + b * ns, max_iter, tol,
+                                                           iters + b, resid + b);
+  }
+  return 0;
+}
+
+int cmpc_sim_equilibrium(cmpc_sim* m, int max_iter, double tol) {
+  if (!m) return fail("cmpc_sim_equilibrium: null simulator");
+  if (equilibrium_check("cmpc_sim_equilibrium", max_iter, tol)) return -1;
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t Bz = (size_t)m->B;
+  if (!m->eq_status) HIP_TRY(hipMalloc(&m->eq_status, sizeof(int32_t) * Bz));
+  if (!m->eq_iters) HIP_TRY(hipMalloc(&m->eq_iters, sizeof(int32_t) * Bz));
+  if (!m->eq_resid) HIP_TRY(hipMalloc(&m->eq_resid, sizeof(double) * Bz));
+  EquilibriumParams P;
+  std::memset(&P, 0, sizeof P);
+  P.x = m->x;
+  P.u_full = m->u_full;
+  P.sim_status = m->status;
+  P.pressures = m->pr;  // the per-scenario instance reads scenario b's pair at this launch
+  P.status = m->eq_status;
+  P.iters = m->eq_iters;
+  P.resid = m->eq_resid;
+  P.B = m->B;
+  P.max_iter = max_iter;
+  P.tol = tol;
+  P.p_in = m->p_in;
+  P.p_out = m->p_out;
+  if (cmpc_launch_equilibrium(P, m->plant, m->stream)) return fail("equilibrium launch failed");
+  return check_launch("equilibrium kernel");
+}
+
+int cmpc_sim_equilibrium_download(cmpc_sim* m, int32_t* status, int32_t* iters, double* resid) {
+  if (!m) return fail("cmpc_sim_equilibrium_download: null simulator");
+  if (!m->eq_status) return fail("cmpc_sim_equilibrium_download: call cmpc_sim_equilibrium first");
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t Bz = (size_t)m->B, bi = sizeof(int32_t) * Bz, br = sizeof(double) * Bz;
+  auto up = [](size_t v) { return (v + 15) / 16 * 16; };
+  const size_t oi = up(br), os = oi + up(bi);
+  if (pinned_acquire(m->pin_out, os + bi)) return -1;
+  char* h = m->pin_out.buf;
+  if (resid) HIP_TRY(hipMemcpyAsync(h, m->eq_resid, br, hipMemcpyDeviceToHost, m->stream));
+  if (iters) HIP_TRY(hipMemcpyAsync(h + oi, m->eq_iters, bi, hipMemcpyDeviceToHost, m->stream));
+  if (status) HIP_TRY(hipMemcpyAsync(h + os, m->eq_status, bi, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  if (resid) std::memcpy(resid, h, br);
+  if (iters) std::memcpy(iters, h + oi, bi);
+  if (status) std::memcpy(status, h + os, bi);
+  return 0;
+}
+
+int32_t* cmpc_sim_equilibrium_status(cmpc_sim* m) { return m ? m->eq_status : nullptr; }
+int32_t* cmpc_sim_equilibrium_iters(cmpc_sim* m) { return m ? m->eq_iters : nullptr; }
+double* cmpc_sim_equilibrium_resid(cmpc_sim* m) { return m ? m->eq_resid : nullptr; }
 
 int cmpc_sim_output(cmpc_sim* m, double* y) {
   if (!m || !y) return fail("null argument");

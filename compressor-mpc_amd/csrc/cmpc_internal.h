@@ -630,6 +630,20 @@ int cmpc_launch_sim(const SimParams& P, int plant, void* stream);
 int cmpc_launch_sim_pressures(const SimParamsP& P, int plant, void* stream);  // -1 without the array
 int cmpc_launch_sim_input(const SimInputParams& P, void* stream);
 int cmpc_launch_sim_output(int plant, const double* x, double* y, int B, void* stream);
+// Plant equilibrium (equilibrium.hip, cmpc_sim_equilibrium)
+struct EquilibriumParams {
+  double* x;                  // B * ns, in and out (written where the status is CMPC_EQ_OK)
+  const double* u_full;       // B * n_inputs
+  const int32_t* sim_status;  // B or null: nonzero leaves the scenario alone (CMPC_EQ_SKIPPED)
+  const double* pressures;    // B * 2, [p_in, p_out] per scenario, 16-byte aligned; null: p_in, p_out
+  int32_t* status;            // B: CMPC_EQ_*
+  int32_t* iters;             // B
+  double* resid;              // B
+  int B, max_iter;
+  double tol, p_in, p_out;
+};
+// four scenarios per wave; -1: unknown plant, max_iter outside [0, 64] or a null array
+int cmpc_launch_equilibrium(const EquilibriumParams& P, int plant, void* stream);
 
 int cmpc_launch_produce(const ProduceParams& P, int plant, void* stream);
 int cmpc_obs_prior_shape(int n_aug, int nd, int nu_tot);

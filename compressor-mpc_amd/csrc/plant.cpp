@@ -106,6 +106,19 @@ int cmpc_plant_output(int plant, const double* x, double* y) {
   return -1;
 }
 
+// GetDerivative of the plant: dx = f(x, u_full) at the boundary pressures
+int cmpc_plant_derivative(int plant, double p_in, double p_out, const double* x, const double* u_full,
+                          double* dx) {
+  if (!x || !u_full || !dx) return -1;
+  if (plant == CMPC_PLANT_PARALLEL)
+    parallel_derivative(p_in, p_out, x, u_full, dx);
+  else if (plant == CMPC_PLANT_SERIAL)
+    serial_derivative(p_in, p_out, x, u_full, dx);
+  else
+    return -1;
+  return 0;
+}
+
 int cmpc_plant_lin_record(int plant, double p_in, double p_out, double Ts, const double* x,
                           const double* u_full, const int32_t* input_order, const int32_t* out_idx,
                           const cmpc_dims* d, double* rec) {

@@ -1178,6 +1178,55 @@ int cmpc_sim_set_pressures(cmpc_sim* sim, const double* pressures_device /* B*2 
 int cmpc_sim_set_pressures_host(cmpc_sim* sim, const double* pressures /* B*2, host */);
 int cmpc_sim_bind_pressures(cmpc_sim* sim, const double* pressures_device /* B*2 */);
 int cmpc_sim_get_pressures(cmpc_sim* sim, double* pressures /* B*2, host */);
+/* Plant equilibrium: for each scenario the state x with
+ * f(x, u, p) = 0 at its plant input and boundary pressures, by Newton's method
+ * from the x given.  Each iteration linearises the plant (A and f as
+ * cmpc_plant_lin_record does before it discretises), takes r = max|f_i| and
+ * solves A d = -f by Gaussian elimination with partial pivoting; host and
+ * device run the same arithmetic (csrc/equilibrium_body.h) and agree bit for
+ * bit.  Per scenario: a status, the iteration that returned and the last r.
+ *   CMPC_EQ_OK              r <= tol; x is the equilibrium
+ *   CMPC_EQ_NO_CONVERGENCE  r > tol after max_iter Newton steps
+ *   CMPC_EQ_NONFINITE       f or A had a non-finite entry (no forward-flow
+ *                           equilibrium at these pressures, as a rule)
+ *   CMPC_EQ_SINGULAR        a zero or non-finite pivot
+ *   CMPC_EQ_SKIPPED         the simulator's status of the scenario was nonzero
+ *                           (a failed integration): not touched
+ * Every status but CMPC_EQ_OK leaves the scenario's x as it was on entry, and
+ * none of them is an error of the call.  max_iter in [0, 64] (0: only test the
+ * x given), tol finite and > 0; 20 and 1e-12 are the defaults of the Python
+ * layer (plain Newton from cmpc_plant_default needs at most 5 steps to 1e-12
+ * for pressures within 5 % of 1 and input offsets within 0.02).
+ *   cmpc_plant_derivative        dx = f(x, u_full) of one state (host); -1: a
+ *                                null pointer or an unknown plant
+ *   cmpc_plant_equilibrium_host  B scenarios on the host, no device: pressures
+ *                                B x 2, u_full B x n_inputs, x B x ns in and out
+ *   cmpc_sim_equilibrium         the simulator's scenarios on its stream, one
+ *                                launch: from its current x, at its current
+ *                                plant input and the pressures in force (the
+ *                                scalars, or the array set or bound); x is
+ *                                written in place; the step sizes and the
+ *                                delay lines stay as they are
+ *   cmpc_sim_equilibrium_download  host copies of the last solve's results
+ *                                (any pointer may be NULL); synchronises
+ *   cmpc_sim_equilibrium_status, _iters, _resid  the device arrays (B each;
+ *                                NULL before the first cmpc_sim_equilibrium) */
+#define CMPC_EQ_OK 0
+#define CMPC_EQ_NO_CONVERGENCE 1
+#define CMPC_EQ_NONFINITE 2
+#define CMPC_EQ_SINGULAR 3
+#define CMPC_EQ_SKIPPED 4
+#define CMPC_EQ_MAX_ITER 64
+int cmpc_plant_derivative(int plant, double p_in, double p_out, const double* x, const double* u_full,
+                          double* dx);
+int cmpc_plant_equilibrium_host(int plant, int B, const double* pressures /* B*2 */,
+                                const double* u_full /* B*n_inputs */, double* x /* B*ns, in/out */,
+                                int max_iter, double tol, int32_t* status, int32_t* iters, double* resid);
+int cmpc_sim_equilibrium(cmpc_sim* sim, int max_iter, double tol);
+int cmpc_sim_equilibrium_download(cmpc_sim* sim, int32_t* status, int32_t* iters, double* resid);
+int32_t* cmpc_sim_equilibrium_status(cmpc_sim* sim);
+int32_t* cmpc_sim_equilibrium_iters(cmpc_sim* sim);
+double* cmpc_sim_equilibrium_resid(cmpc_sim* sim);
 /* NerveCenter::UpdateUOld (nerve_center.h:313-319): u_control (device,
  * B x nu_tot, plant control order) += each sub-controller's first move of its
  * own inputs (du_old after cmpc_iterate; input_order as cmpc_produce_lin). */
