@@ -29,7 +29,10 @@ from .configs import ControllerConfig, SetupFile, reference_config, reference_ob
 from .problem import ControllerArrays, controller_arrays, plant_input_from_plans
 from ._abi import (CMPC_EQ_OK, CMPC_EQ_NO_CONVERGENCE, CMPC_EQ_NONFINITE, CMPC_EQ_SINGULAR,  # noqa: F401
                    CMPC_EQ_SKIPPED)
+from ._abi import (CMPC_EIG_OK, CMPC_EIG_NO_CONVERGENCE, CMPC_EIG_NONFINITE, CMPC_EIG_SKIPPED,  # noqa: F401
+                   CMPC_EIG_MAX_ITER, CMPC_MODES_NSUM)
 from .sim import plant_derivative, plant_equilibrium  # noqa: F401
+from .sim import eig_batch, eig_batch_device, modes_summary, plant_modes  # noqa: F401
 
 __all__ = ["Context", "ControllerConfig", "SetupFile", "reference_config", "reference_setup",
            "reference_observer_gain", "controller_arrays",
@@ -46,7 +49,9 @@ __all__ = ["Context", "ControllerConfig", "SetupFile", "reference_config", "refe
            "CMPC_NOISE_STREAM_MEASUREMENT", "CMPC_NOISE_STREAM_INPUT",
            "quantile_check", "quantile_rank", "quantile_value", "quantiles_host", "envelope_check", "envelope_len",
            "plant_derivative", "plant_equilibrium", "CMPC_EQ_OK", "CMPC_EQ_NO_CONVERGENCE", "CMPC_EQ_NONFINITE",
-           "CMPC_EQ_SINGULAR", "CMPC_EQ_SKIPPED"]
+           "CMPC_EQ_SINGULAR", "CMPC_EQ_SKIPPED",
+           "eig_batch", "eig_batch_device", "modes_summary", "plant_modes", "CMPC_EIG_OK", "CMPC_EIG_NO_CONVERGENCE",
+           "CMPC_EIG_NONFINITE", "CMPC_EIG_SKIPPED", "CMPC_EIG_MAX_ITER", "CMPC_MODES_NSUM"]
 
 
 def layout_of(dims: CmpcDims) -> CmpcLayout:

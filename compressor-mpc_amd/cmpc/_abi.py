@@ -168,6 +168,9 @@ EXPORTS = (
     "cmpc_plant_derivative", "cmpc_plant_equilibrium_host", "cmpc_sim_equilibrium",
     "cmpc_sim_equilibrium_download", "cmpc_sim_equilibrium_status", "cmpc_sim_equilibrium_iters",
     "cmpc_sim_equilibrium_resid",
+    "cmpc_eig_host", "cmpc_eig_device", "cmpc_modes_summary_host", "cmpc_plant_modes_host", "cmpc_sim_modes",
+    "cmpc_sim_modes_download", "cmpc_sim_modes_wr", "cmpc_sim_modes_wi", "cmpc_sim_modes_summary",
+    "cmpc_sim_modes_status", "cmpc_sim_modes_iters",
 )
 
 # per-scenario statuses of the equilibrium solve (include/cmpc.h)
@@ -177,6 +180,17 @@ CMPC_EQ_NONFINITE = 2
 CMPC_EQ_SINGULAR = 3
 CMPC_EQ_SKIPPED = 4
 CMPC_EQ_MAX_ITER = 64
+
+# per-matrix statuses of the eigenvalue solver and the summary of the plant
+# modes (include/cmpc.h)
+CMPC_EIG_OK = 0
+CMPC_EIG_NO_CONVERGENCE = 1
+CMPC_EIG_NONFINITE = 2
+CMPC_EIG_SKIPPED = 3
+CMPC_EIG_MAX_N = 12
+CMPC_EIG_MAX_ITER = 360
+CMPC_MODES_NSUM = 6
+MODES_SUMMARY = ("abscissa", "n_unstable", "zeta_min", "omega_d", "omega_n", "re_min")
 
 # the fields of a slot's score record, in the record's order (cmpc_score_field
 # gives each one's rows; include/cmpc.h has the table)
@@ -419,6 +433,20 @@ def load_library(path: str = LIB_PATH):
         "cmpc_sim_equilibrium_status": ([c_void], c_void),
         "cmpc_sim_equilibrium_iters": ([c_void], c_void),
         "cmpc_sim_equilibrium_resid": ([c_void], c_void),
+        "cmpc_eig_host": ([ctypes.c_int, ctypes.c_int, P(dbl), ctypes.c_int, P(dbl), P(dbl), P(i32), P(i32)],
+                          ctypes.c_int),
+        "cmpc_eig_device": ([ctypes.c_int, ctypes.c_int, c_void, ctypes.c_int, c_void, c_void, c_void, c_void,
+                             c_void], ctypes.c_int),
+        "cmpc_modes_summary_host": ([ctypes.c_int, ctypes.c_int, P(dbl), P(dbl), P(i32), P(dbl)], ctypes.c_int),
+        "cmpc_plant_modes_host": ([ctypes.c_int, ctypes.c_int, P(dbl), P(dbl), P(dbl), ctypes.c_int, P(dbl), P(dbl),
+                                   P(dbl), P(i32), P(i32)], ctypes.c_int),
+        "cmpc_sim_modes": ([c_void, ctypes.c_int], ctypes.c_int),
+        "cmpc_sim_modes_download": ([c_void, P(dbl), P(dbl), P(dbl), P(i32), P(i32)], ctypes.c_int),
+        "cmpc_sim_modes_wr": ([c_void], c_void),
+        "cmpc_sim_modes_wi": ([c_void], c_void),
+        "cmpc_sim_modes_summary": ([c_void], c_void),
+        "cmpc_sim_modes_status": ([c_void], c_void),
+        "cmpc_sim_modes_iters": ([c_void], c_void),
         "cmpc_qp_solve_batch": ([ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P(dbl),
                                  P(dbl), P(dbl), P(dbl), P(dbl), P(dbl), P(u32), ctypes.c_int,
                                  P(dbl), P(i32), P(i32), P(u32), P(ctypes.c_uint8), P(i32)],

@@ -28,6 +28,7 @@ batched over B scenarios on the device:
 Everything between two records runs on the GPU (sim.hip, observer.hip,
 produce.hip, cmpc_kernels.hip); torch tensors are the device buffers.
 """
+import collections
 import time
 
 import numpy as np
@@ -35,6 +36,11 @@ import numpy as np
 from . import CMPC_TRACE, Context, scenario_limits, scenario_reference_offsets
 from .configs import ControllerConfig
 from .sim import EQ_MAX_ITER, EQ_TOL, REF_CONTROL_INDEX, REF_DELAYS, REF_EPS, REF_TS, PlantSimulator
+
+# ClosedLoop.modes: the summary's columns (include/cmpc.h, _abi.MODES_SUMMARY),
+# the eigenvalues and the statuses
+PlantModes = collections.namedtuple("PlantModes", ("abscissa", "n_unstable", "zeta_min", "omega_d", "omega_n",
+                                                   "re_min", "w", "status"))
 
 
 def _fmt(v: float) -> str:
@@ -501,6 +507,17 @@ class ClosedLoop:
         out = self.sim.equilibrium(max_iter, tol)
         self.x0 = self.torch.from_numpy(self.sim.download()[0]).to(self.dev)
         return out
+
+    def modes(self, max_iter=None) -> "PlantModes":
+        """The plant's open-loop modes at the loop's current states (after
+        trim or initialize), under the plant pressures in force
+        (PlantSimulator.modes, one launch; nothing of the loop is written):
+        a PlantModes record of (B,) arrays abscissa, n_unstable, zeta_min,
+        omega_d, omega_n, re_min (include/cmpc.h has the summary), the
+        eigenvalues w (B, ns) complex and status (B,)."""
+        w, sm, status, _ = self.sim.modes(max_iter)
+        return PlantModes(sm[:, 0].copy(), sm[:, 1].copy(), sm[:, 2].copy(), sm[:, 3].copy(), sm[:, 4].copy(),
+                          sm[:, 5].copy(), w, status)
 
     def initialize(self, dx_init=None):
         """SimulationSystem(x0, u_offset) + NerveCenter::Initialize(x0, 0,

@@ -8,7 +8,7 @@ import ctypes
 
 import numpy as np
 
-from ._abi import check, dptr, iptr, load_library
+from ._abi import CMPC_EIG_MAX_N, CMPC_MODES_NSUM, check, dptr, iptr, load_library
 
 REF_DELAYS = (0, 40, 0, 40)          # Delays of both plants (control-input order)
 REF_CONTROL_INDEX = (0, 3, 4, 7)     # ControlInputIndex: plant input of each control input
@@ -56,6 +56,97 @@ def plant_equilibrium(plant: int, pressures, u_full, x0, max_iter: int = EQ_MAX_
     check(lib.cmpc_plant_equilibrium_host(plant, B, dptr(p), dptr(u), dptr(x), max_iter, tol, iptr(status),
                                           iptr(iters), dptr(resid)), "cmpc_plant_equilibrium_host")
     return x, status, iters, resid
+
+
+def _eig_iter(max_iter, n: int) -> int:
+    """The QR sweeps allowed per matrix: 30 n unless given."""
+    return 30 * n if max_iter is None else int(max_iter)
+
+
+def _complex(wr, wi) -> np.ndarray:
+    """wr + i wi with both parts kept bit for bit (a NaN's pattern included)."""
+    w = np.empty(wr.shape, np.complex128)
+    w.real, w.imag = wr, wi
+    return w
+
+
+def eig_batch(A, max_iter=None):
+    """Eigenvalues of B real n x n matrices, 1 <= n <= 12, on the host
+    (cmpc_eig_host, no device): A (B, n, n).  Returns (w, status, iters): w
+    (B, n) complex128 ordered by real part descending, then imaginary part
+    descending (NaN where status is not CMPC_EIG_OK), status and iters (B,)
+    int32.  max_iter: QR sweeps allowed per matrix (default 30 n)."""
+    a = np.ascontiguousarray(A, np.float64)
+    if a.ndim != 3 or a.shape[0] < 1 or a.shape[1] != a.shape[2] or not 1 <= a.shape[1] <= CMPC_EIG_MAX_N:
+        raise ValueError(f"A must be (B, n, n) with B >= 1 and 1 <= n <= {CMPC_EIG_MAX_N}, got {a.shape}")
+    B, n = a.shape[:2]
+    wr, wi = np.zeros((B, n)), np.zeros((B, n))
+    status, iters = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    check(load_library().cmpc_eig_host(n, B, dptr(a), _eig_iter(max_iter, n), dptr(wr), dptr(wi), iptr(status),
+                                       iptr(iters)), "cmpc_eig_host")
+    return _complex(wr, wi), status, iters
+
+
+def eig_batch_device(A, max_iter=None):
+    """eig_batch on the device (cmpc_eig_device, one launch on torch's current
+    stream): A a contiguous float64 device tensor (B, n, n), n = 10 or 11.
+    Returns (wr, wi, status, iters) as device tensors ((B, n) float64 twice,
+    (B,) int32 twice); the arithmetic is eig_batch's, bit for bit."""
+    import torch
+    if (not isinstance(A, torch.Tensor) or A.dim() != 3 or A.shape[0] < 1 or A.shape[1] != A.shape[2]
+            or A.shape[1] not in (10, 11) or A.dtype != torch.float64 or not A.is_cuda or not A.is_contiguous()):
+        raise ValueError("A must be a contiguous float64 device tensor (B, n, n) with n = 10 or 11")
+    B, n = int(A.shape[0]), int(A.shape[1])
+    wr, wi = torch.zeros(B, n, dtype=torch.float64, device=A.device), torch.zeros(B, n, dtype=torch.float64,
+                                                                                  device=A.device)
+    status = torch.zeros(B, dtype=torch.int32, device=A.device)
+    iters = torch.zeros(B, dtype=torch.int32, device=A.device)
+    vp = ctypes.c_void_p
+    with torch.cuda.device(A.device):
+        check(load_library().cmpc_eig_device(n, B, vp(A.data_ptr()), _eig_iter(max_iter, n), vp(wr.data_ptr()),
+                                             vp(wi.data_ptr()), vp(status.data_ptr()), vp(iters.data_ptr()),
+                                             vp(torch.cuda.current_stream(A.device).cuda_stream)),
+              "cmpc_eig_device")
+    return wr, wi, status, iters
+
+
+def modes_summary(w, status) -> np.ndarray:
+    """(B, 6): the summary of include/cmpc.h (_abi.MODES_SUMMARY names the
+    columns) of ordered eigenvalues w (B, n) complex, NaN where status is not
+    CMPC_EIG_OK (cmpc_modes_summary_host)."""
+    w = np.asarray(w, np.complex128)
+    st = np.ascontiguousarray(status, np.int32)
+    if w.ndim != 2 or w.shape[0] < 1 or not 1 <= w.shape[1] <= CMPC_EIG_MAX_N or st.shape != (w.shape[0],):
+        raise ValueError(f"w must be (B, n) with 1 <= n <= {CMPC_EIG_MAX_N} and status (B,), got {w.shape} and "
+                         f"{st.shape}")
+    wr, wi = np.ascontiguousarray(w.real), np.ascontiguousarray(w.imag)
+    out = np.zeros((w.shape[0], CMPC_MODES_NSUM))
+    check(load_library().cmpc_modes_summary_host(w.shape[1], w.shape[0], dptr(wr), dptr(wi), iptr(st), dptr(out)),
+          "cmpc_modes_summary_host")
+    return out
+
+
+def plant_modes(plant: int, pressures, u_full, x, max_iter=None):
+    """The plant's modes for B scenarios on the host (no device): the
+    eigenvalues of the continuous Jacobian df/dx at x (B, ns) under pressures
+    (B, 2) and the plant input u_full (B, n_inputs).  Returns (w, summary,
+    status, iters): w (B, ns) complex128 in eig_batch's order, summary (B, 6)
+    (_abi.MODES_SUMMARY names the columns); the arithmetic is
+    PlantSimulator.modes', bit for bit."""
+    lib = load_library()
+    ns, ni = _plant_sizes(lib, plant)
+    xs = np.ascontiguousarray(x, np.float64)
+    B = xs.shape[0] if xs.ndim == 2 else 0
+    p = np.ascontiguousarray(pressures, np.float64)
+    u = np.ascontiguousarray(u_full, np.float64)
+    if B < 1 or xs.shape != (B, ns) or p.shape != (B, 2) or u.shape != (B, ni):
+        raise ValueError(f"x must be (B, {ns}), pressures (B, 2) and u_full (B, {ni}), "
+                         f"got {xs.shape}, {p.shape} and {u.shape}")
+    wr, wi, sm = np.zeros((B, ns)), np.zeros((B, ns)), np.zeros((B, CMPC_MODES_NSUM))
+    status, iters = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    check(lib.cmpc_plant_modes_host(plant, B, dptr(p), dptr(u), dptr(xs), _eig_iter(max_iter, ns), dptr(wr), dptr(wi),
+                                    dptr(sm), iptr(status), iptr(iters)), "cmpc_plant_modes_host")
+    return _complex(wr, wi), sm, status, iters
 
 
 class PlantSimulator:
@@ -186,6 +277,19 @@ class PlantSimulator:
         check(self.lib.cmpc_sim_equilibrium_download(self._h, iptr(status), iptr(iters), dptr(resid)),
               "cmpc_sim_equilibrium_download")
         return status, iters, resid
+
+    def modes(self, max_iter=None):
+        """The plant's modes at every scenario's current state, plant input
+        and the pressures in force (one launch; nothing of the simulator is
+        written): the eigenvalues of the continuous Jacobian df/dx.  Returns
+        (w, summary, status, iters) as plant_modes does; a scenario whose
+        simulator status is nonzero reports CMPC_EIG_SKIPPED with NaN."""
+        check(self.lib.cmpc_sim_modes(self._h, _eig_iter(max_iter, self.ns)), "cmpc_sim_modes")
+        wr, wi, sm = np.zeros((self.B, self.ns)), np.zeros((self.B, self.ns)), np.zeros((self.B, CMPC_MODES_NSUM))
+        status, iters = np.zeros(self.B, np.int32), np.zeros(self.B, np.int32)
+        check(self.lib.cmpc_sim_modes_download(self._h, dptr(wr), dptr(wi), dptr(sm), iptr(status), iptr(iters)),
+              "cmpc_sim_modes_download")
+        return _complex(wr, wi), sm, status, iters
 
     def output(self, out=None):
         """GetOutput into out (B, n_outputs) (default: self.y)."""

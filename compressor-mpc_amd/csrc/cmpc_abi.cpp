@@ -21,6 +21,7 @@
 
 #include "dispatch.h"
 #include "ensemble_select.h"
+#include "eig_body.h"
 #include "equilibrium_body.h"
 #include "noise_body.h"
 
@@ -1556,6 +1557,10 @@ struct cmpc_sim {
   // results of the last cmpc_sim_equilibrium (B each, allocated on first use)
   int32_t *eq_status = nullptr, *eq_iters = nullptr;
   double* eq_resid = nullptr;
+  // results of the last cmpc_sim_modes (allocated on first use): wr, wi B * ns,
+  // summary B * CMPC_MODES_NSUM, status and iters B
+  double *md_wr = nullptr, *md_wi = nullptr, *md_summary = nullptr;
+  int32_t *md_status = nullptr, *md_iters = nullptr;
   PinnedIO pin_in, pin_out;  // host-array calls: page-locked staging
 };
 
@@ -1619,7 +1624,8 @@ int cmpc_sim_destroy(cmpc_sim* m) {
   pinned_free(m->pin_in);
   pinned_free(m->pin_out);
   void* bufs[] = {m->x, m->dt, m->u_full, m->u_offset, m->ring, m->scratch, m->stage, m->status, m->own_pr,
-                  m->eq_status, m->eq_iters, m->eq_resid};
+                  m->eq_status, m->eq_iters, m->eq_resid, m->md_wr, m->md_wi, m->md_summary, m->md_status,
+                  m->md_iters};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (m->own_stream && m->stream) (void)hipStreamDestroy(m->stream);
@@ -1911,6 +1917,147 @@ int cmpc_sim_equilibrium_download(cmpc_sim* m, int32_t* status, int32_t* iters, 
 int32_t* cmpc_sim_equilibrium_status(cmpc_sim* m) { return m ? m->eq_status : nullptr; }
 int32_t* cmpc_sim_equilibrium_iters(cmpc_sim* m) { return m ? m->eq_iters : nullptr; }
 double* cmpc_sim_equilibrium_resid(cmpc_sim* m) { return m ? m->eq_resid : nullptr; }
+
+// Eigenvalues and plant modes (include/cmpc.h, eig_body.h, eig.hip)
+static int eig_check(const char* who, int max_iter) {
+  if (max_iter < 1 || max_iter > CMPC_EIG_MAX_ITER)
+    return fail(std::string(who) + ": max_iter must be in [1, " + std::to_string(CMPC_EIG_MAX_ITER) + "]");
+  return 0;
+}
+
+int cmpc_eig_host(int n, int B, const double* A, int max_iter, double* wr, double* wi, int32_t* status,
+                  int32_t* iters) {
+  if (n < 1 || n > CMPC_EIG_MAX_N)
+    return fail("cmpc_eig_host: n must be in [1, " + std::to_string(CMPC_EIG_MAX_N) + "]");
+  if (B < 1) return fail("cmpc_eig_host: B must be >= 1");
+  if (!A || !wr || !wi || !status || !iters) return fail("cmpc_eig_host: null argument");
+  if (eig_check("cmpc_eig_host", max_iter)) return -1;
+  const size_t nz = (size_t)n;
+  for (size_t b = 0; b < (size_t)B; ++b)
+    status[b] = cmpc_eig::eig_host(n, A + b * nz * nz, max_iter, wr + b * nz, wi + b * nz, iters + b, nullptr);
+  return 0;
+}
+
+int cmpc_eig_device(int n, int B, const double* A, int max_iter, double* wr, double* wi, int32_t* status,
+                    int32_t* iters, void* stream) {
+  if (n != 10 && n != 11) return fail("cmpc_eig_device: n must be 10 or 11");
+  if (B < 1) return fail("cmpc_eig_device: B must be >= 1");
+  if (!A || !wr || !wi || !status || !iters) return fail("cmpc_eig_device: null argument");
+  if (eig_check("cmpc_eig_device", max_iter)) return -1;
+  EigParams P;
+  std::memset(&P, 0, sizeof P);
+  P.A = A;
+  P.wr = wr;
+  P.wi = wi;
+  P.status = status;
+  P.iters = iters;
+  P.B = B;
+  P.max_iter = max_iter;
+  if (cmpc_launch_eig(P, n, stream)) return fail("cmpc_eig_device: launch failed");
+  return check_launch("eig kernel");
+}
+
+int cmpc_modes_summary_host(int n, int B, const double* wr, const double* wi, const int32_t* status,
+                            double* summary) {
+  if (n < 1 || n > CMPC_EIG_MAX_N)
+    return fail("cmpc_modes_summary_host: n must be in [1, " + std::to_string(CMPC_EIG_MAX_N) + "]");
+  if (B < 1) return fail("cmpc_modes_summary_host: B must be >= 1");
+  if (!wr || !wi || !status || !summary) return fail("cmpc_modes_summary_host: null argument");
+  for (size_t b = 0; b < (size_t)B; ++b)
+    cmpc_eig::eig_summary(n, wr + b * n, wi + b * n, status[b] == CMPC_EIG_OK, summary + b * CMPC_MODES_NSUM);
+  return 0;
+}
+
+extern "C++" {
+template <int PLANT>
+static int plant_modes_one(double p_in, double p_out, const double* u, const double* x, int max_iter, double* wr,
+                           double* wi, double* summary, int32_t* iters) {
+  constexpr int ns = cmpc_eq::Dims<PLANT>::ns;
+  double A[ns * ns], Bm[ns * 4], C[4 * ns], f[ns];
+  cmpc_eq::eq_linearize<PLANT>(p_in, p_out, x, u, A, Bm, C, f);
+  return cmpc_eig::eig_host_one<ns>(A, max_iter, wr, wi, iters, summary);
+}
+}  // extern "C++"
+
+int cmpc_plant_modes_host(int plant, int B, const double* pressures, const double* u_full, const double* x,
+                          int max_iter, double* wr, double* wi, double* summary, int32_t* status, int32_t* iters) {
+  int ns = 0, ni = 0, no = 0, nci = 0;
+  if (cmpc_plant_dims(plant, &ns, &ni, &no, &nci)) return fail("cmpc_plant_modes_host: unknown plant");
+  if (B < 1) return fail("cmpc_plant_modes_host: B must be >= 1");
+  if (!pressures || !u_full || !x || !wr || !wi || !summary || !status || !iters)
+    return fail("cmpc_plant_modes_host: null argument");
+  if (eig_check("cmpc_plant_modes_host", max_iter)) return -1;
+  for (size_t b = 0; b < (size_t)B; ++b) {
+    const double p_in = pressures[2 * b], p_out = pressures[2 * b + 1];
+    double *r = wr + b * ns, *i = wi + b * ns, *s = summary + b * CMPC_MODES_NSUM;
+    status[b] = plant == CMPC_PLANT_PARALLEL
+                    ? plant_modes_one<CMPC_PLANT_PARALLEL>(p_in, p_out, u_full + b * ni, x + b * ns, max_iter, r, i, s,
+                                                           iters + b)
+                    : plant_modes_one<CMPC_PLANT_SERIAL>(p_in, p_out, u_full + b * ni, x + b * ns, max_iter, r, i, s,
+                                                         iters + b);
+  }
+  return 0;
+}
+
+int cmpc_sim_modes(cmpc_sim* m, int max_iter) {
+  if (!m) return fail("cmpc_sim_modes: null simulator");
+  if (eig_check("cmpc_sim_modes", max_iter)) return -1;
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t Bz = (size_t)m->B;
+  if (!m->md_wr) HIP_TRY(hipMalloc(&m->md_wr, sizeof(double) * Bz * m->ns));
+  if (!m->md_wi) HIP_TRY(hipMalloc(&m->md_wi, sizeof(double) * Bz * m->ns));
+  if (!m->md_summary) HIP_TRY(hipMalloc(&m->md_summary, sizeof(double) * Bz * CMPC_MODES_NSUM));
+  if (!m->md_status) HIP_TRY(hipMalloc(&m->md_status, sizeof(int32_t) * Bz));
+  if (!m->md_iters) HIP_TRY(hipMalloc(&m->md_iters, sizeof(int32_t) * Bz));
+  ModesParams P;
+  std::memset(&P, 0, sizeof P);
+  P.x = m->x;
+  P.u_full = m->u_full;
+  P.sim_status = m->status;
+  P.pressures = m->pr;  // the per-scenario instance reads scenario b's pair at this launch
+  P.wr = m->md_wr;
+  P.wi = m->md_wi;
+  P.summary = m->md_summary;
+  P.status = m->md_status;
+  P.iters = m->md_iters;
+  P.B = m->B;
+  P.max_iter = max_iter;
+  P.p_in = m->p_in;
+  P.p_out = m->p_out;
+  if (cmpc_launch_modes(P, m->plant, m->stream)) return fail("modes launch failed");
+  return check_launch("modes kernel");
+}
+
+int cmpc_sim_modes_download(cmpc_sim* m, double* wr, double* wi, double* summary, int32_t* status,
+                            int32_t* iters) {
+  if (!m) return fail("cmpc_sim_modes_download: null simulator");
+  if (!m->md_status) return fail("cmpc_sim_modes_download: call cmpc_sim_modes first");
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t Bz = (size_t)m->B, bw = sizeof(double) * Bz * m->ns, bs = sizeof(double) * Bz * CMPC_MODES_NSUM,
+               bi = sizeof(int32_t) * Bz;
+  auto up = [](size_t v) { return (v + 15) / 16 * 16; };
+  const size_t o_wi = up(bw), o_sm = o_wi + up(bw), o_st = o_sm + up(bs), o_it = o_st + up(bi);
+  if (pinned_acquire(m->pin_out, o_it + bi)) return -1;
+  char* h = m->pin_out.buf;
+  if (wr) HIP_TRY(hipMemcpyAsync(h, m->md_wr, bw, hipMemcpyDeviceToHost, m->stream));
+  if (wi) HIP_TRY(hipMemcpyAsync(h + o_wi, m->md_wi, bw, hipMemcpyDeviceToHost, m->stream));
+  if (summary) HIP_TRY(hipMemcpyAsync(h + o_sm, m->md_summary, bs, hipMemcpyDeviceToHost, m->stream));
+  if (status) HIP_TRY(hipMemcpyAsync(h + o_st, m->md_status, bi, hipMemcpyDeviceToHost, m->stream));
+  if (iters) HIP_TRY(hipMemcpyAsync(h + o_it, m->md_iters, bi, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  if (wr) std::memcpy(wr, h, bw);
+  if (wi) std::memcpy(wi, h + o_wi, bw);
+  if (summary) std::memcpy(summary, h + o_sm, bs);
+  if (status) std::memcpy(status, h + o_st, bi);
+  if (iters) std::memcpy(iters, h + o_it, bi);
+  return 0;
+}
+
+double* cmpc_sim_modes_wr(cmpc_sim* m) { return m ? m->md_wr : nullptr; }
+double* cmpc_sim_modes_wi(cmpc_sim* m) { return m ? m->md_wi : nullptr; }
+double* cmpc_sim_modes_summary(cmpc_sim* m) { return m ? m->md_summary : nullptr; }
+int32_t* cmpc_sim_modes_status(cmpc_sim* m) { return m ? m->md_status : nullptr; }
+int32_t* cmpc_sim_modes_iters(cmpc_sim* m) { return m ? m->md_iters : nullptr; }
 
 int cmpc_sim_output(cmpc_sim* m, double* y) {
   if (!m || !y) return fail("null argument");

@@ -644,6 +644,30 @@ struct EquilibriumParams {
 };
 // four scenarios per wave; -1: unknown plant, max_iter outside [0, 64] or a null array
 int cmpc_launch_equilibrium(const EquilibriumParams& P, int plant, void* stream);
+// Eigenvalues and plant modes (eig.hip, cmpc_eig_device, cmpc_sim_modes)
+struct EigParams {
+  const double* A;   // B * n * n, row-major blocks
+  double *wr, *wi;   // B * n
+  int32_t* status;   // B: CMPC_EIG_*
+  int32_t* iters;    // B
+  int B, max_iter;
+};
+struct ModesParams {
+  const double* x;            // B * ns, read only
+  const double* u_full;       // B * n_inputs
+  const int32_t* sim_status;  // B or null: nonzero gives CMPC_EIG_SKIPPED
+  const double* pressures;    // B * 2, [p_in, p_out] per scenario, 16-byte aligned; null: p_in, p_out
+  double *wr, *wi;            // B * ns
+  double* summary;            // B * CMPC_MODES_NSUM
+  int32_t* status;            // B: CMPC_EIG_*
+  int32_t* iters;             // B
+  int B, max_iter;
+  double p_in, p_out;
+};
+// four matrices per wave; -1: n not 10 or 11, an unknown plant, max_iter outside
+// [1, CMPC_EIG_MAX_ITER] or a null array
+int cmpc_launch_eig(const EigParams& P, int n, void* stream);
+int cmpc_launch_modes(const ModesParams& P, int plant, void* stream);
 
 int cmpc_launch_produce(const ProduceParams& P, int plant, void* stream);
 int cmpc_obs_prior_shape(int n_aug, int nd, int nu_tot);

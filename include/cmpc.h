@@ -1227,6 +1227,75 @@ int cmpc_sim_equilibrium_download(cmpc_sim* sim, int32_t* status, int32_t* iters
 int32_t* cmpc_sim_equilibrium_status(cmpc_sim* sim);
 int32_t* cmpc_sim_equilibrium_iters(cmpc_sim* sim);
 double* cmpc_sim_equilibrium_resid(cmpc_sim* sim);
+/* Plant modes: the eigenvalues of small real nonsymmetric
+ * matrices in batches, and on top of them the modes of the plant, that is the
+ * eigenvalues of the continuous Jacobian A = df/dx at each scenario's state
+ * (an equilibrium after cmpc_sim_equilibrium, but any state gives a valid A).
+ * Per matrix: scaling by powers of two (Parlett-Reinsch), Householder
+ * reduction to Hessenberg form, Francis double-shift QR with deflation; no
+ * eigenvectors.  Host and device run the same arithmetic (csrc/eig_body.h) and
+ * agree bit for bit.  Per matrix: wr and wi (n each), a status, and iters, the
+ * QR sweeps used (<= max_iter).
+ *   CMPC_EIG_OK              all n eigenvalues found
+ *   CMPC_EIG_NO_CONVERGENCE  more than max_iter QR sweeps would be needed (or
+ *                            an eigenvalue overflowed)
+ *   CMPC_EIG_NONFINITE       an entry of the matrix was not finite
+ *   CMPC_EIG_SKIPPED         the simulator's status of the scenario was nonzero
+ * None of them is an error of the call.  The eigenvalues are ordered by real
+ * part descending, then imaginary part descending: a conjugate pair sits
+ * together, the member with wi > 0 first, the real parts equal bit for bit and
+ * wi[k + 1] == -wi[k].  For every status but CMPC_EIG_OK wr, wi and the summary
+ * are the quiet NaN 0x7ff8000000000000.  max_iter in [1, CMPC_EIG_MAX_ITER];
+ * the Python layer's default is 30 n.
+ * The summary, CMPC_MODES_NSUM doubles per matrix, from the ordered values:
+ *   [0] spectral abscissa, max Re
+ *   [1] the number of eigenvalues with Re > 0
+ *   [2] the least damping ratio zeta = -Re / |lambda| over the eigenvalues with
+ *       Im > 0 (the first in the order on a tie); 1 when there is none
+ *   [3] that eigenvalue's damped frequency Im (0 when none)
+ *   [4] its natural frequency |lambda| = sqrt(Re Re + Im Im) (0 when none)
+ *   [5] min Re, the fastest mode
+ *   cmpc_eig_host            B matrices (row-major n x n blocks, 1 <= n <= 12)
+ *                            on the host, no device
+ *   cmpc_eig_device          the same on the current device, n = 10 or 11 (a
+ *                            smaller matrix is embedded block-diagonally); all
+ *                            arrays device pointers; asynchronous on stream
+ *   cmpc_modes_summary_host  the summary of eigenvalues given (B x n, ordered),
+ *                            NaN where status is not CMPC_EIG_OK
+ *   cmpc_plant_modes_host    B scenarios of the plant on the host: pressures
+ *                            B x 2, u_full B x n_inputs, x B x ns; wr, wi B x ns,
+ *                            summary B x 6
+ *   cmpc_sim_modes           the simulator's scenarios on its stream, one
+ *                            launch: at its current x and plant input and the
+ *                            pressures in force; x is not written
+ *   cmpc_sim_modes_download  host copies of the last analysis (any pointer may
+ *                            be NULL); synchronises
+ *   cmpc_sim_modes_wr, _wi, _summary, _status, _iters  the device arrays (NULL
+ *                            before the first cmpc_sim_modes) */
+#define CMPC_EIG_OK 0
+#define CMPC_EIG_NO_CONVERGENCE 1
+#define CMPC_EIG_NONFINITE 2
+#define CMPC_EIG_SKIPPED 3
+#define CMPC_EIG_MAX_N 12
+#define CMPC_EIG_MAX_ITER 360 /* 30 * CMPC_EIG_MAX_N */
+#define CMPC_MODES_NSUM 6
+int cmpc_eig_host(int n, int B, const double* A /* B*n*n */, int max_iter, double* wr /* B*n */,
+                  double* wi /* B*n */, int32_t* status, int32_t* iters);
+int cmpc_eig_device(int n, int B, const double* A_device, int max_iter, double* wr_device, double* wi_device,
+                    int32_t* status_device, int32_t* iters_device, void* stream);
+int cmpc_modes_summary_host(int n, int B, const double* wr, const double* wi, const int32_t* status,
+                            double* summary /* B*6 */);
+int cmpc_plant_modes_host(int plant, int B, const double* pressures /* B*2 */,
+                          const double* u_full /* B*n_inputs */, const double* x /* B*ns */, int max_iter,
+                          double* wr, double* wi, double* summary /* B*6 */, int32_t* status, int32_t* iters);
+int cmpc_sim_modes(cmpc_sim* sim, int max_iter);
+int cmpc_sim_modes_download(cmpc_sim* sim, double* wr, double* wi, double* summary, int32_t* status,
+                            int32_t* iters);
+double* cmpc_sim_modes_wr(cmpc_sim* sim);
+double* cmpc_sim_modes_wi(cmpc_sim* sim);
+double* cmpc_sim_modes_summary(cmpc_sim* sim);
+int32_t* cmpc_sim_modes_status(cmpc_sim* sim);
+int32_t* cmpc_sim_modes_iters(cmpc_sim* sim);
 /* NerveCenter::UpdateUOld (nerve_center.h:313-319): u_control (device,
  * B x nu_tot, plant control order) += each sub-controller's first move of its
  * own inputs (du_old after cmpc_iterate; input_order as cmpc_produce_lin). */
