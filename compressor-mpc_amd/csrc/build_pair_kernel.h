@@ -53,6 +53,42 @@
 #endif
 static_assert(CMPC_PAIR_ZDEPTH == 1 || CMPC_PAIR_ZDEPTH == 2, "CMPC_PAIR_ZDEPTH");
 
+// Diagnostic build (tools/rows_timing.py ... pair), as CMPC_ROWS_TIMING in
+// build_rows_kernel.h: per-wave s_memtime cycle totals of a group's phases,
+// written over the QP output (results invalid).  Slots: 0 staging issue,
+// 1 staging wait, 2 head compare, 3 w tables, 4 the rest of the prologue,
+// 5 horizon loop, 6 epilogue and back edge.  Reading the counter drains the
+// LDS queue, so a phase is charged the latency of what it issued.
+#ifndef CMPC_PAIR_TIMING
+#define CMPC_PAIR_TIMING 0
+#endif
+// Two A/B arms of the set-up (profiles/pair_setup_ab).  SETUP_PRIO runs a
+// group's staging and set-up at top issue priority and drops to the
+// fair-progress level at the first horizon step: the set-up's few VALU no
+// longer queue behind the partner wave's FMA stream (headline build 212.9 ->
+// 210.1 us; on).  TOUCH reads one dword of every 128-byte line of the wave's
+// next group of records at the start of the last horizon segment, so that its
+// staging would find them in the L2: 233.7 us, as the row kernel's prefetch
+// (off).
+#ifndef CMPC_PAIR_SETUP_PRIO
+#define CMPC_PAIR_SETUP_PRIO 1
+#endif
+#ifndef CMPC_PAIR_TOUCH
+#define CMPC_PAIR_TOUCH 0
+#endif
+#if CMPC_PAIR_TIMING
+#define CMPC_PT(i)                                         \
+  {                                                        \
+    __builtin_amdgcn_sched_barrier(0);                     \
+    const uint64_t now_ = __builtin_amdgcn_s_memtime();    \
+    tsum[i] += now_ - tlast;                               \
+    tlast = now_;                                          \
+    __builtin_amdgcn_sched_barrier(0);                     \
+  }
+#else
+#define CMPC_PT(i)
+#endif
+
 // Wait for the staging DMA.  This is an S_WAITCNT instruction of the compiler's
 // own (vmcnt(0), the other counters left alone), not inline assembly: a
 // global_load_lds counts on vmcnt and on lgkmcnt, so the wait-count pass keeps
@@ -199,38 +235,49 @@ void cmpc_build_pair_kernel(BuildParams P) {
   const int g_first = blockIdx.x * WPG + wave;
   int done_groups = 0;
   uint32_t shared_scn = 0;
+#if CMPC_PAIR_TIMING
+  uint64_t tsum[7] = {0, 0, 0, 0, 0, 0, 0}, tlast = __builtin_amdgcn_s_memtime();
+  const uint64_t t0c = tlast, t0r = __builtin_amdgcn_s_memrealtime();
+  int ngrp = 0;
+#endif
   __builtin_amdgcn_s_setprio(3);
+  float touch[3] = {0.f, 0.f, 0.f};
   for (int g = g_first; g < ngroups; g += nwaves) {
-    {
-      const int level = 3 - (4 * done_groups) / share;  // fair progress (build_rows_kernel.h)
+    CMPC_PT(6)  // back edge
+    const int level = 3 - (4 * done_groups) / share;  // fair progress (build_rows_kernel.h)
+    ++done_groups;
+    auto fair_prio = [&]() {
       if (level <= 0) __builtin_amdgcn_s_setprio(0);
       else if (level == 1) __builtin_amdgcn_s_setprio(1);
       else if (level == 2) __builtin_amdgcn_s_setprio(2);
-      ++done_groups;
-    }
+    };
+    if (CMPC_PAIR_SETUP_PRIO) __builtin_amdgcn_s_setprio(3);
+    else fair_prio();
     const int scn = 4 * g + R;
     const bool qv = scn < nscn;
     const int scc = qv ? scn : nscn - 1;
     const int nsc = min(4, nscn - 4 * g);
     const double* gbase = P.lin + (size_t)8 * g * rl;
     // pass h: slot h's records whole, slot 1 - h's from t0 on
-    auto stage = [&](int h) {
+    // (ln: the lane; pass 1 hands in an opaque copy, so that the addresses of
+    // its rare restaging are formed there and not kept across the horizon loop)
+    auto stage = [&](int h, int ln) {
 #pragma unroll
       for (int sc = 0; sc < 4; ++sc) {
         if (sc >= nsc) break;
-        const double* rec = gbase + (2 * sc + h) * rl + 2 * lane;
-        const double* tal = gbase + (2 * sc + 1 - h) * rl + t0 + 2 * lane;
+        const double* rec = gbase + (2 * sc + h) * rl + 2 * ln;
+        const double* tal = gbase + (2 * sc + 1 - h) * rl + t0 + 2 * ln;
         double* dst = wreg + sc * sps;
         auto* gp = (__attribute__((address_space(1))) void*)rec;
         auto* lp = (__attribute__((address_space(3))) void*)dst;
         // rec_len <= 384: at most three blocks
         if (wch >= 64) __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
-        else if (lane < wch) __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
+        else if (ln < wch) __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
         if (wch >= 128) __builtin_amdgcn_global_load_lds(gp, lp, 16, 1024, 0);
-        else if (lane < wch - 64) __builtin_amdgcn_global_load_lds(gp, lp, 16, 1024, 0);
+        else if (ln < wch - 64) __builtin_amdgcn_global_load_lds(gp, lp, 16, 1024, 0);
         if (wch >= 192) __builtin_amdgcn_global_load_lds(gp, lp, 16, 2048, 0);
-        else if (lane < wch - 128) __builtin_amdgcn_global_load_lds(gp, lp, 16, 2048, 0);
-        if (lane < tch)  // tch <= 64 (cmpc_pair_layout)
+        else if (ln < wch - 128) __builtin_amdgcn_global_load_lds(gp, lp, 16, 2048, 0);
+        if (ln < tch)  // tch <= 64 (cmpc_pair_layout)
           __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)tal,
                                            (__attribute__((address_space(3))) void*)(dst + rl), 16, 0, 0);
       }
@@ -240,7 +287,7 @@ void cmpc_build_pair_kernel(BuildParams P) {
     // ---- one round trip: slot 0's records + slot 1's tails -> LDS, slot 1's heads -> registers ----
     // (the previous group's LDS stores have landed before the DMA writes over them)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    stage(0);
+    stage(0, lane);
     // entries 64 i + lane < 64 NCMP <= rec_len of slot 1's record (those from
     // hd on are masked out of the compare); a partial group's missing
     // scenarios repeat its last one: no branch, no read outside the batch
@@ -268,7 +315,10 @@ void cmpc_build_pair_kernel(BuildParams P) {
 #pragma unroll
         for (int o2 = 0; o2 < NY; ++o2) dyr[s][o2] = P.dy_ref[qo + s * NY + o2];
     }
+    CMPC_PT(0)  // staging issue
     pair_wait_dma();
+    CMPC_PT(1)  // staging wait
+    if (CMPC_PAIR_TOUCH) asm volatile("" ::"v"(touch[0]), "v"(touch[1]), "v"(touch[2]));  // (loaded; not used)
     uint64_t diff = 0ull;
 #pragma unroll
     for (int sc = 0; sc < 4; ++sc) {
@@ -281,6 +331,7 @@ void cmpc_build_pair_kernel(BuildParams P) {
     }
     const bool mism = __ballot(diff != 0ull) != 0ull;
     if (!mism) shared_scn += (uint32_t)nsc;
+    CMPC_PT(2)  // head compare
 
     for (int h = 0;; ++h) {  // the shared pass, or pass 0 and pass 1 of a group that differs
       // (opaque copies of the lane's position: what is derived from them is
@@ -297,9 +348,86 @@ void cmpc_build_pair_kernel(BuildParams P) {
         xa[s] = tb + P.off_x;
         yv[s] = tb + P.off_y;
       }
-      // delay-line inputs of both QPs, AdjustAllDelayedStates applied; zero once
-      // the line has drained.  The w tables lie behind the staged records
-      // (PairLayout), so they are written while the records are still read.
+      // ---- set-up: two batches of LDS reads, no branch ----
+      // A lane without a role reads the zero slots, or an entry that a lane
+      // with the role reads anyway and drops the value by a select; a lane
+      // with nothing to store stores to the row's dump slot, as in the loop.
+      // A guarded link of an FMA chain is computed and the old accumulator kept
+      // by a select where the guard is false, so the chain's bits are those
+      // of the guarded form.
+      //
+      // Batch 1: every read of the staged records.  The w tables' sources are
+      // the delay-line inputs of both QPs (entry t of line k: x_aug[ndist + k]
+      // at t = 0, then x_aug[boff[k] + t - 1]); a lane whose entry lies past the
+      // line's length or the table's reads entry t = 0 instead, which lane 0
+      // reads, and its store goes to the dump slot: those table entries are
+      // zero from the kernel's start and nothing else writes the tables.
+      static_assert(U * NY <= 16, "one zero-restore store per lane");
+      static_assert((NUT & (NUT - 1)) == 0, "column rotation by a mask");
+      // (the lane's role indices from the opaque copy, as above)
+      const int oog = ol ? jg - NS : 0, kcg = cl ? jg - (16 - ND) : 0, cmg = mk ? jg - NS : 0;
+      double wv[2][ND][4];
+      bool wlive[ND][4];
+#pragma unroll
+      for (int k = 0; k < ND; ++k)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int t = jg + 16 * i;  // WL <= 64 (cmpc_pair_layout)
+          wlive[k][i] = t < WL && t < dlen[k];
+          const int src = (wlive[k][i] && t > 0) ? boff[k] + t - 1 : ndist + k;
+#pragma unroll
+          for (int s = 0; s < 2; ++s) wv[s][k][i] = xa[s][src];
+        }
+      const bool jo = j < nobs;
+      double cs[NY];
+      {
+        const double* src = jo ? srec + P.off_C + jg : zeros;
+        const int str = jo ? nobs : 0;
+#pragma unroll
+        for (int o2 = 0; o2 < NY; ++o2) cs[o2] = src[o2 * str];
+      }
+      constexpr int KX = 16 - NS;
+      double kx[2][KX], ky[2][NY];
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+#pragma unroll
+        for (int d = 0; d < KX; ++d) kx[s][d] = xa[s][(d < ndist) ? d : 0];
+#pragma unroll
+        for (int o2 = 0; o2 < NY; ++o2) ky[s][o2] = yv[s][o2];
+      }
+      double mP[NS];
+      {
+        const double* src = st ? srec + P.off_A + jg : mk ? srec + P.off_B + ((cmg + rot) & (NUT - 1)) : zeros;
+        const int str = st ? NS : mk ? NUT : 0;
+#pragma unroll
+        for (int l = 0; l < NS; ++l) mP[l] = src[l * str];
+      }
+      double ma[NS], mb[ND], fj;
+      {
+        // (16 zero slots: NS, NUT <= 16)
+        const double* arow = st ? srec + P.off_A + jg * NS : zeros;
+        const double* brow = st ? srec + P.off_B + jg * NUT : zeros;
+        const double* frow = st ? srec + P.off_f + jg : zeros;
+#pragma unroll
+        for (int l = 0; l < NS; ++l) ma[l] = arow[l];
+#pragma unroll
+        for (int k = 0; k < ND; ++k) mb[k] = brow[(dinp[k] + rot) % NUT];
+        fj = *frow;
+      }
+      double lu[NY][NY];  // L_W' (upper triangle), the same for every lane
+#pragma unroll
+      for (int o = 0; o < NY; ++o)
+#pragma unroll
+        for (int o2 = o; o2 < NY; ++o2) lu[o][o2] = lwt[o * NY + o2];
+      // every staged read is issued before the first write over the staged records below
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int o2 = 0; o2 < NY; ++o2) ky[s][o2] = ky[s][o2] - dyr[s][o2];
+
+      // the w tables (AdjustAllDelayedStates applied; the entries past a line's
+      // length stay zero), then the C_hat rows, which may lie over the dump slots
 #pragma unroll
       for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -307,117 +435,94 @@ void cmpc_build_pair_kernel(BuildParams P) {
           double* wk = wtab + ((Rg * 2 + s) * ND + k) * WL;
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            const int t = jg + 16 * i;  // WL <= 64 (cmpc_pair_layout)
-            if (t < WL)
-              wk[t] = (t < dlen[k]) ? ((t == 0) ? xa[s][ndist + k] : xa[s][boff[k] + t - 1]) - uo[s][k] : 0.0;
+            const int t = jg + 16 * i;
+            double* dst = wlive[k][i] ? wk + t : dump;
+            *dst = wv[s][k][i] - uo[s][k];
           }
         }
-      double cs[NY];
-#pragma unroll
-      for (int o2 = 0; o2 < NY; ++o2) cs[o2] = (j < nobs) ? srec[P.off_C + o2 * nobs + jg] : 0.0;
-      constexpr int KX = 16 - NS;
-      double kx[2][KX], ky[2][NY];
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-#pragma unroll
-        for (int d = 0; d < KX; ++d) kx[s][d] = (d < ndist) ? xa[s][d] : 0.0;
-#pragma unroll
-        for (int o2 = 0; o2 < NY; ++o2) ky[s][o2] = yv[s][o2];
-#pragma unroll
-        for (int o2 = 0; o2 < NY; ++o2) ky[s][o2] = ky[s][o2] - dyr[s][o2];
-      }
-      double mP[NS];
-      if (st) {
-        const double* src = srec + P.off_A + jg;
-#pragma unroll
-        for (int l = 0; l < NS; ++l) mP[l] = src[l * NS];
-      } else if (mk) {
-        const double* src = srec + P.off_B + (cm + rot) % NUT;
-#pragma unroll
-        for (int l = 0; l < NS; ++l) mP[l] = src[l * NUT];
-      } else {
-#pragma unroll
-        for (int l = 0; l < NS; ++l) mP[l] = 0.0;
-      }
-      double mS[NS + ND], fj = 0.0;
-      if (st) {
-        const double* arow = srec + P.off_A + jg * NS;
-        const double* brow = srec + P.off_B + jg * NUT;
-#pragma unroll
-        for (int l = 0; l < NS; ++l) mS[l] = arow[l];
-#pragma unroll
-        for (int k = 0; k < ND; ++k) mS[NS + k] = brow[(dinp[k] + rot) % NUT];
-        fj = srec[P.off_f + jg];
-      } else {
-#pragma unroll
-        for (int l = 0; l < NS + ND; ++l) mS[l] = 0.0;
-      }
-      // every staged read is issued before the first write over the staged records below
-      __builtin_amdgcn_sched_barrier(0);
-
+      CMPC_PT(3)  // staged reads and w tables
       double pP[NY];
 #pragma unroll
       for (int o = 0; o < NY; ++o) {
         double t = 0.0;
 #pragma unroll
         for (int o2 = 0; o2 < NY; ++o2)
-          if (o2 >= o) t = __builtin_fma(lwt[o * NY + o2], cs[o2], t);
-        if (j < nobs) chq[o * 16 + jg] = t;
+          if (o2 >= o) t = __builtin_fma(lu[o][o2], cs[o2], t);
+        // every lane stores its own entry of the row: an entry from nobs on is
+        // never used (below), and a store to the dump slot instead could hit
+        // another row's C_hat entry in the same instruction (the rows overlay
+        // the hand-off areas, dump slots included)
+        chq[o * 16 + jg] = t;
         pP[o] = st ? t : 0.0;
       }
-      double base0 = 0.0, base1 = 0.0, pS0 = 0.0, pS1 = 0.0, yh0 = 0.0, yh1 = 0.0;
-      const double *yp0 = zeros, *yp1 = zeros;
-      int yinc = 0;
-      if (st) {
-        base0 = base1 = fj;
-        pS0 = pS1 = fj;
-        // x_1 = f + Adelay w_0, each slot's delayed inputs in its own order
+
+      // Batch 2: what the stores above hand over.  Row oo of C_hat (an output
+      // lane's multipliers and its kappa factors), the lane's weight row and
+      // y_ref heads, a carrier's w_1 and w_2, a state lane's w_0 of every line.
+      const double* yl = ylT + oog * yls;
+      const double* wk0 = cl ? wtab + ((Rg * 2 + 0) * ND + kcg) * WL : zeros;
+      const double* wk1 = cl ? wtab + ((Rg * 2 + 1) * ND + (ND - 1 - kcg)) * WL : zeros;
+      double ch[16], lw[NY], w0[2][ND];
 #pragma unroll
-        for (int k = 0; k < ND; ++k) {
-          pS0 = __builtin_fma(mS[NS + k], wtab[((Rg * 2 + 0) * ND + k) * WL], pS0);
-          pS1 = __builtin_fma(mS[NS + ND - 1 - k], wtab[((Rg * 2 + 1) * ND + k) * WL], pS1);
-        }
-      } else if (ol) {
+      for (int l = 0; l < 16; ++l) ch[l] = chq[oog * 16 + l];
 #pragma unroll
-        for (int l = 0; l < NS; ++l) mS[l] = chq[oo * 16 + l];
-        double t[2] = {0.0, 0.0};
+      for (int o2 = 0; o2 < NY; ++o2) lw[o2] = lwt[oog * NY + o2];
 #pragma unroll
-        for (int s = 0; s < 2; ++s) {
+      for (int s = 0; s < 2; ++s)
 #pragma unroll
-          for (int d = 0; d < KX; ++d)
-            if (d < ndist) t[s] = __builtin_fma(chq[oo * 16 + NS + d], kx[s][d], t[s]);
+        for (int k = 0; k < ND; ++k) w0[s][k] = wtab[((Rg * 2 + s) * ND + k) * WL];
+      const double yl0 = yl[0], yl1 = yl[NY * yls];
+      const double c01 = wk0[1], c02 = wk0[2], c11 = wk1[1], c12 = wk1[2];
+      // the first steps' zeroed P accumulators (CMPC_PAIR_STEP): read here, ahead
+      // of the stores below, so that the loop's first head waits like the others
+      double z1[NY], z2[NY];
 #pragma unroll
-          for (int o2 = 0; o2 < NY; ++o2)
-            if (o2 >= oo) t[s] = __builtin_fma(lwt[oo * NY + o2], ky[s][o2], t[s]);
-        }
-        base0 = t[0];
-        base1 = t[1];
-        const double* yl = ylT + oo * yls;
-        yh0 = yl[0];
-        yh1 = yl[NY * yls];
-        yp0 = yl + 1;
-        yp1 = yl + NY * yls + 1;
-        yinc = 1;
-      } else if (cl) {
-        const double* wk0 = wtab + ((Rg * 2 + 0) * ND + kc) * WL;
-        const double* wk1 = wtab + ((Rg * 2 + 1) * ND + (ND - 1 - kc)) * WL;
-        pS0 = wk0[1];
-        yh0 = wk0[2];
-        yp0 = wk0 + 3;
-        pS1 = wk1[1];
-        yh1 = wk1[2];
-        yp1 = wk1 + 3;
-        yinc = 1;
-      }
+      for (int o = 0; o < NY; ++o) z1[o] = z2[o] = zeros[o];
       // restore the zero areas the staging and the C_hat rows overwrote
 #pragma unroll
-      for (int c = 0; c < NUT; ++c)
-        if (P.delay[c] > 0 && j < (M - 1) * NY) qlines[P.rows.lo[c] + j] = 0.0;
-      for (int e = j; e < U * NY; e += 16) qlines[P.rows.zr_off + e] = 0.0;
-      if (tl) {
-#pragma unroll
-        for (int o = 0; o < NY; ++o) tq[o] = 0.0;
+      for (int c = 0; c < NUT; ++c) {
+        double* dst = (P.delay[c] > 0 && jg < (M - 1) * NY) ? qlines + P.rows.lo[c] + jg : dump;
+        *dst = 0.0;
       }
+      qlines[P.rows.zr_off + min(jg, U * NY - 1)] = 0.0;
+#pragma unroll
+      for (int o = 0; o < NY; ++o) {
+        double* dst = tl ? tq + o : dump;
+        *dst = 0.0;
+      }
+      // x_1 = f + Adelay w_0, each slot's delayed inputs in its own order
+      double x0 = fj, x1 = fj;
+#pragma unroll
+      for (int k = 0; k < ND; ++k) {
+        x0 = __builtin_fma(mb[k], w0[0][k], x0);
+        x1 = __builtin_fma(mb[ND - 1 - k], w0[1][k], x1);
+      }
+      double kap[2] = {0.0, 0.0};
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+#pragma unroll
+        for (int d = 0; d < KX; ++d) {
+          const double tn = __builtin_fma(ch[NS + d], kx[s][d], kap[s]);
+          kap[s] = (d < ndist) ? tn : kap[s];
+        }
+#pragma unroll
+        for (int o2 = 0; o2 < NY; ++o2) {
+          const double tn = __builtin_fma(lw[o2], ky[s][o2], kap[s]);
+          kap[s] = (o2 >= oog) ? tn : kap[s];
+        }
+      }
+      double mS[NS + ND];
+#pragma unroll
+      for (int l = 0; l < NS; ++l) mS[l] = ol ? ch[l] : ma[l];
+#pragma unroll
+      for (int k = 0; k < ND; ++k) mS[NS + k] = mb[k];
+      // (fj, mb, hence x0 and x1, are zero off the state lanes; c01 .. c12 off the carriers)
+      const double base0 = ol ? kap[0] : fj, base1 = ol ? kap[1] : fj;
+      double pS0 = st ? x0 : c01, pS1 = st ? x1 : c11;
+      double yh0 = ol ? yl0 : c02, yh1 = ol ? yl1 : c12;
+      const double* yp0 = ol ? yl + 1 : wk0 + 3;
+      const double* yp1 = ol ? yl + NY * yls + 1 : wk1 + 3;
+      int yinc = (ol || cl) ? 1 : 0;
       double cv[NY], rd[NY], acc[NC];
 #pragma unroll
       for (int o = 0; o < NY; ++o) cv[o] = rd[o] = 0.0;
@@ -473,10 +578,19 @@ void cmpc_build_pair_kernel(BuildParams P) {
 
       int r = 0;
       double aN0 = base0 + yh0, aN1 = base1 + yh1;  // start values of the next step's free responses
-      double z1[NY], z2[NY];                        // zeroed P accumulators of the coming steps (from LDS)
-#pragma unroll
-      for (int o = 0; o < NY; ++o) z1[o] = z2[o] = zeros[o];
+      CMPC_PT(4)  // the rest of the prologue
+      if (CMPC_PAIR_SETUP_PRIO) fair_prio();
       for (int sg = 0; sg <= nseg; ++sg) {
+        if (CMPC_PAIR_TOUCH && sg == nseg) {
+          // the wave's next group (its own again after the last): 8 records, 3 x 64 lines
+          // of 128 bytes cover rec_len <= 384; clamped into the group's records
+          const int gn = (g + nwaves < ngroups) ? g + nwaves : g;
+          const char* nb = reinterpret_cast<const char*>(P.lin + (size_t)8 * gn * rl);
+          const int nbytes = 2 * min(4, nscn - 4 * gn) * rl * (int)sizeof(double);
+#pragma unroll
+          for (int i = 0; i < 3; ++i)
+            touch[i] = *reinterpret_cast<const float*>(nb + min((lane + 64 * i) * 128, nbytes - 4));
+        }
         int r_end = pp;
 #pragma unroll
         for (int i = 0; i < NSEG; ++i)
@@ -520,22 +634,30 @@ void cmpc_build_pair_kernel(BuildParams P) {
 #pragma unroll
       for (int o = 0; o < NY; ++o) cv[o] = __builtin_fma(smask, cv[o], rd[o]);
       rows_pair_gacc<NY, NUT, M>(cv, acc);  // row p - 1
+#if CMPC_PAIR_TIMING
+#pragma unroll
+      for (int a = 0; a < NC; ++a) asm volatile("" ::"v"(acc[a]));  // the stores below are left out
+#endif
+      CMPC_PT(5)  // horizon loop
 
       // ---- each slot's H, f, G to its own QP in its own column order ----
-      if (qv && gl) {
+      // (addressed from the pass's opaque copies, so that the pointers are formed
+      // here and not kept across the horizon loop)
+      if (qv && gl && !CMPC_PAIR_TIMING) {
         constexpr int nuo = NUT - NU, nVo = M * nuo;
-        const int k2 = j / NUT, c2 = j - k2 * NUT;
+        const int k2 = jg / NUT, c2 = jg - k2 * NUT;
+        const int scg = 4 * g + Rg;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
           if (mism && s != h) continue;
-          double* out = P.qp + (size_t)(2 * scn + s) * P.qp_len;
+          double* out = P.qp + (size_t)(2 * scg + s) * P.qp_len;
           const double* uwt = uw_all + s * NU * NU;
           // slot s's own column a = (ka, ca) is canonical column ka NUT + (ca + s NU) % NUT
           double own[NV];
 #pragma unroll
           for (int a = 0; a < NV; ++a) own[a] = acc[(a / NU) * NUT + (a % NU + s * NU) % NUT];
           if (zlane) {
-            if (j == NC + s) {
+            if (jg == NC + s) {
 #pragma unroll
               for (int a = 0; a < NV; ++a) out[NV * NV + a] = own[a];  // f
             }
@@ -555,14 +677,37 @@ void cmpc_build_pair_kernel(BuildParams P) {
         }
       }
       __builtin_amdgcn_wave_barrier();
+      CMPC_PT(6)  // epilogue
       if (!mism || h == 1) break;
       // pass 1: slot 1's records whole, slot 0's tails
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      stage(1);
+      int l1 = lane;
+      asm volatile("" : "+v"(l1));
+      stage(1, l1);
       pair_wait_dma();
+      CMPC_PT(1)  // restaging, issue and wait
     }
+#if CMPC_PAIR_TIMING
+    ++ngrp;
+#endif
   }
   if (lane == 0 && shared_scn) atomicAdd(P.pair_cnt, shared_scn);
+#if CMPC_PAIR_TIMING
+  // one 16-double record per wave, as far as the QP buffer reaches
+  const size_t wid = (size_t)blockIdx.x * WPG + wave;
+  if (lane == 0 && (wid + 1) * 16 <= (size_t)P.nqp * P.qp_len) {
+    const uint64_t t1c = __builtin_amdgcn_s_memtime(), t1r = __builtin_amdgcn_s_memrealtime();
+    double* dbg = P.qp + wid * 16;
+    for (int i = 0; i < 7; ++i) dbg[i] = (double)tsum[i];
+    dbg[7] = 1.0;
+    dbg[8] = (double)(t1c - t0c);  // shader cycles of the wave's lifetime
+    dbg[9] = (double)(t1r - t0r);  // 100 MHz ticks of the same span
+    dbg[10] = (double)t0r;
+    dbg[11] = (double)t1r;
+    dbg[12] = (double)ngrp;
+    dbg[13] = (double)wid;
+  }
+#endif
 }
 
 template <int NS, int NY, int NU, int M>

@@ -2,7 +2,9 @@
 the one-QP-per-wave kernel (diagnostic library built with -DCMPC_ROWS_TIMING=1
 -DCMPC_WAVE_TIMING=1: tools/build_variant.sh timing "...").  For the wave
 kernel slot 1 is the fused solve (0 here) and a "group" is one QP.
-usage: CMPC_LIBRARY=ab/timing/libcmpc.so python tools/rows_timing.py [p] [B] [plant-ctype] [rows|wave]"""
+KERNEL=pair: the shared form of the row build (build_pair_kernel.h, library
+built with -DCMPC_PAIR_TIMING=1), pairing forced on; a group is four scenarios.
+usage: CMPC_LIBRARY=ab/timing/libcmpc.so python tools/rows_timing.py [p] [B] [plant-ctype] [rows|wave|pair]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "compressor-mpc_amd"))
@@ -19,7 +21,8 @@ arr = cmpc.controller_arrays(cfg, reference_setup(PLANT, CTYPE))
 lin, u, du, ws = synthetic_batch(cfg, B, seed=7, n_distinct=min(B, 256))
 with cmpc.Context(cfg, B) as ctx:
     ctx.configure(arr); ctx.set_state(u, du, ws); ctx.upload_lin(lin)
-    ctx.set_build_variant(cmpc.CMPC_BUILD_ROWS if KERNEL == "rows" else cmpc.CMPC_BUILD_WAVE)
+    ctx.set_build_variant(cmpc.CMPC_BUILD_WAVE if KERNEL == "wave" else cmpc.CMPC_BUILD_ROWS)
+    ctx.set_build_pairing(cmpc.CMPC_PAIRING_ON if KERNEL == "pair" else cmpc.CMPC_PAIRING_OFF)
     import time
     t_end = time.perf_counter() + 0.3  # settle at the steady clock
     while time.perf_counter() < t_end:
@@ -31,9 +34,33 @@ with cmpc.Context(cfg, B) as ctx:
     ctx.synchronize()
     kms, _ = ctx.kernel_time(cmpc.CMPC_KERNEL_BUILD)
     print(f"build kernel (events): {kms * 1e3:.2f} us")
+    shared = ctx.last_build_shared_scenarios()
     H, f, G = ctx.download_qp()
 raw = np.concatenate([H.reshape(H.shape[0], -1), f, G.reshape(G.shape[0], -1)], axis=1).reshape(-1)
 d = raw[: (raw.size // 16) * 16].reshape(-1, 16)
+if KERNEL == "pair":
+    # one record per wave: 0..6 the phase totals, 7 the mark, 8 cycles and 9 100 MHz ticks of
+    # the wave's lifetime, 10 / 11 its start and end, 12 its groups, 13 its index
+    d = d[(d[:, 7] == 1.0) & (d[:, 13] == np.arange(len(d)))]
+    ng = d[:, 12].sum()
+    assert shared == B and ng == -(-B // 4), (shared, ng)
+    names = ["staging issue", "staging wait", "head compare", "w tables", "rest of prologue", "horizon loop",
+             "epilogue/back edge"]
+    tot = d[:, :7].sum()
+    print(f"pair kernel, {PLANT}-{CTYPE} p={p}: {len(d)} waves, {ng:.0f} groups; s_memtime cycles per group:")
+    for i, n_ in enumerate(names):
+        print(f"  {n_:18s} {d[:, i].sum() / ng:10.0f}  ({d[:, i].sum() / tot * 100:5.1f} %)")
+    setup = d[:, :5].sum() / tot
+    print(f"  staging + set-up (slots 0-4): {setup * 100:.1f} % of the attributed cycles; attributed / lifetime "
+          f"{tot / d[:, 8].sum():.3f}")
+    clk = d[:, 8] / (d[:, 9] / 100e6) / 1e9
+    print(f"  in-kernel shader clock: median {np.median(clk):.3f} GHz (min {clk.min():.3f}, max {clk.max():.3f})")
+    print(f"  kernel span: {(d[:, 11].max() - d[:, 10].min()) / 100e6 * 1e3:.4f} ms; wave lifetime ms: min "
+          f"{d[:, 9].min() / 1e5:.4f} median {np.median(d[:, 9]) / 1e5:.4f} max {d[:, 9].max() / 1e5:.4f}")
+    for n_ in np.unique(d[:, 12]):
+        m_ = d[:, 12] == n_
+        print(f"  waves with {n_:.0f} groups: {m_.sum()}")
+    sys.exit(0)
 d = d[d[:, 7] == 1.0]
 ng = d[:, 6].sum()
 names = ["tail/back-edge", "staging issue", "staging wait", "prologue compute", "horizon loop", "epilogue"]
