@@ -168,6 +168,9 @@ EXPORTS = (
     "cmpc_plant_derivative", "cmpc_plant_equilibrium_host", "cmpc_sim_equilibrium",
     "cmpc_sim_equilibrium_download", "cmpc_sim_equilibrium_status", "cmpc_sim_equilibrium_iters",
     "cmpc_sim_equilibrium_resid",
+    "cmpc_target_check", "cmpc_plant_target_host", "cmpc_sim_target", "cmpc_sim_target_host",
+    "cmpc_sim_target_download", "cmpc_sim_target_status", "cmpc_sim_target_iters", "cmpc_sim_target_resid",
+    "cmpc_sim_delay_len", "cmpc_sim_download_inputs",
     "cmpc_eig_host", "cmpc_eig_device", "cmpc_modes_summary_host", "cmpc_plant_modes_host", "cmpc_sim_modes",
     "cmpc_sim_modes_download", "cmpc_sim_modes_wr", "cmpc_sim_modes_wi", "cmpc_sim_modes_summary",
     "cmpc_sim_modes_status", "cmpc_sim_modes_iters",
@@ -179,6 +182,7 @@ CMPC_EQ_NO_CONVERGENCE = 1
 CMPC_EQ_NONFINITE = 2
 CMPC_EQ_SINGULAR = 3
 CMPC_EQ_SKIPPED = 4
+CMPC_EQ_DEADZONE = 5   # the target solve only: a free recycle valve below 2e-2
 CMPC_EQ_MAX_ITER = 64
 
 # per-matrix statuses of the eigenvalue solver and the summary of the plant
@@ -433,6 +437,18 @@ def load_library(path: str = LIB_PATH):
         "cmpc_sim_equilibrium_status": ([c_void], c_void),
         "cmpc_sim_equilibrium_iters": ([c_void], c_void),
         "cmpc_sim_equilibrium_resid": ([c_void], c_void),
+        "cmpc_target_check": ([ctypes.c_int, ctypes.c_int, P(i32), P(i32), ctypes.c_int, dbl, dbl], ctypes.c_int),
+        "cmpc_plant_target_host": ([ctypes.c_int, ctypes.c_int, P(dbl), ctypes.c_int, P(i32), P(i32), P(dbl), P(dbl),
+                                    P(dbl), ctypes.c_int, dbl, dbl, P(i32), P(i32), P(dbl)], ctypes.c_int),
+        "cmpc_sim_target": ([c_void, ctypes.c_int, P(i32), P(i32), c_void, ctypes.c_int, dbl, dbl], ctypes.c_int),
+        "cmpc_sim_target_host": ([c_void, ctypes.c_int, P(i32), P(i32), P(dbl), ctypes.c_int, dbl, dbl],
+                                 ctypes.c_int),
+        "cmpc_sim_target_download": ([c_void, P(i32), P(i32), P(dbl)], ctypes.c_int),
+        "cmpc_sim_target_status": ([c_void], c_void),
+        "cmpc_sim_target_iters": ([c_void], c_void),
+        "cmpc_sim_target_resid": ([c_void], c_void),
+        "cmpc_sim_delay_len": ([c_void], ctypes.c_int),
+        "cmpc_sim_download_inputs": ([c_void, P(dbl), P(dbl)], ctypes.c_int),
         "cmpc_eig_host": ([ctypes.c_int, ctypes.c_int, P(dbl), ctypes.c_int, P(dbl), P(dbl), P(i32), P(i32)],
                           ctypes.c_int),
         "cmpc_eig_device": ([ctypes.c_int, ctypes.c_int, c_void, ctypes.c_int, c_void, c_void, c_void, c_void,

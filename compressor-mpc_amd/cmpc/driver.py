@@ -35,12 +35,15 @@ import numpy as np
 
 from . import CMPC_TRACE, Context, scenario_limits, scenario_reference_offsets
 from .configs import ControllerConfig
-from .sim import EQ_MAX_ITER, EQ_TOL, REF_CONTROL_INDEX, REF_DELAYS, REF_EPS, REF_TS, PlantSimulator
+from .sim import (EQ_MAX_ITER, EQ_TOL, REF_CONTROL_INDEX, REF_DELAYS, REF_EPS, REF_TS, TARGET_TOL_Y,
+                  PlantSimulator)
 
 # ClosedLoop.modes: the summary's columns (include/cmpc.h, _abi.MODES_SUMMARY),
 # the eigenvalues and the statuses
 PlantModes = collections.namedtuple("PlantModes", ("abscissa", "n_unstable", "zeta_min", "omega_d", "omega_n",
                                                    "re_min", "w", "status"))
+# ClosedLoop.trim_to_outputs: the solve's results and the free inputs in force
+TrimTargets = collections.namedtuple("TrimTargets", ("status", "iters", "resid", "u_free", "du_free"))
 
 
 def _fmt(v: float) -> str:
@@ -507,6 +510,43 @@ class ClosedLoop:
         out = self.sim.equilibrium(max_iter, tol)
         self.x0 = self.torch.from_numpy(self.sim.download()[0]).to(self.dev)
         return out
+
+    def trim_to_outputs(self, hold, targets, free=None, max_iter: int = EQ_MAX_ITER, tol_f: float = EQ_TOL,
+                        tol_y: float = TARGET_TOL_Y) -> "TrimTargets":
+        """Start every scenario at rest with given outputs (call before
+        initialize): as trim, but the plant outputs `hold`
+        are brought to `targets` ((nh,) or (B, nh), plant-output units) by
+        solving for as many control inputs `free` as well (columns of B: 0 and
+        2 the torques, 1 and 3 the recycle valves; None: the torques, in order,
+        for up to two held outputs).  The plant is reset to x0 and u_offset,
+        the plant's pressures are put in force, PlantSimulator.target solves on
+        the device, and where the status is CMPC_EQ_OK x0 and the free columns
+        of u_offset become the solution; each scenario's change of its free
+        inputs is added to every pending set_segments offset, so a later
+        disturbance step keeps the trimmed inputs.  A scenario with any other
+        status keeps its given x0 and offset.  Returns a TrimTargets record:
+        status, iters (B,), resid (B, 2) of (max|f|, max|y - t|), u_free
+        (B, nh) the free inputs in force and du_free their change."""
+        hold = [int(h) for h in np.asarray(hold).reshape(-1)]
+        if free is None:
+            if len(hold) > 2:
+                raise ValueError("trim_to_outputs: give `free` for more than two held outputs")
+            free = [0, 2][:len(hold)]
+        free = [int(f) for f in np.asarray(free).reshape(-1)]
+        self.sim.reset(self.x0, self.u_offset, self.Ts)
+        self.k = 0
+        self._pressure_rows()
+        before = self.u_offset.cpu().numpy()
+        status, iters, resid = self.sim.target(hold, free, targets, max_iter, tol_f, tol_y)
+        cols = [REF_CONTROL_INDEX[f] for f in free]
+        after = self.sim.download_inputs()[0]
+        du = after[:, cols] - before[:, cols]
+        self.x0 = self.torch.from_numpy(self.sim.download()[0]).to(self.dev)
+        self.u_offset = self._plant_offset = self.torch.from_numpy(after).to(self.dev)
+        if cols:
+            for _, off in self._sched:
+                off[:, cols] += self.torch.from_numpy(du).to(self.dev)
+        return TrimTargets(status, iters, resid, np.ascontiguousarray(after[:, cols]), du)
 
     def modes(self, max_iter=None) -> "PlantModes":
         """The plant's open-loop modes at the loop's current states (after

@@ -16,6 +16,7 @@ REF_TS = 0.05                        # sampling time of results/*.dat
 REF_EPS = 1e-6                       # Integrate's max_rel_error / max_abs_error
 EQ_MAX_ITER = 20                     # equilibrium solve: Newton steps allowed and the
 EQ_TOL = 1e-12                       # bound on max|f|
+TARGET_TOL_Y = 1e-10                 # target solve: bound on max|y - t|
 
 
 def _plant_sizes(lib, plant: int):
@@ -56,6 +57,54 @@ def plant_equilibrium(plant: int, pressures, u_full, x0, max_iter: int = EQ_MAX_
     check(lib.cmpc_plant_equilibrium_host(plant, B, dptr(p), dptr(u), dptr(x), max_iter, tol, iptr(status),
                                           iptr(iters), dptr(resid)), "cmpc_plant_equilibrium_host")
     return x, status, iters, resid
+
+
+def _target_indices(lib, plant: int, hold, free, max_iter: int, tol_f: float, tol_y: float):
+    """hold and free as int32 arrays of one length, checked by cmpc_target_check."""
+    h = np.ascontiguousarray(hold, np.int32).reshape(-1)
+    f = np.ascontiguousarray(free, np.int32).reshape(-1)
+    if len(h) != len(f):
+        raise ValueError(f"as many free inputs as held outputs: got {len(f)} and {len(h)}")
+    check(lib.cmpc_target_check(plant, len(h), iptr(h), iptr(f), max_iter, tol_f, tol_y), "cmpc_target_check")
+    return h, f
+
+
+def _target_array(targets, B: int, nh: int) -> np.ndarray:
+    """targets as (B, nh): (nh,) holds for every scenario."""
+    t = np.asarray(targets, np.float64)
+    if t.shape == (nh,):
+        t = np.broadcast_to(t, (B, nh))
+    if t.shape != (B, nh):
+        raise ValueError(f"targets must be ({nh},) or ({B}, {nh}), got {t.shape}")
+    return np.ascontiguousarray(t)
+
+
+def plant_target(plant: int, pressures, hold, free, targets, u_full, x0, max_iter: int = EQ_MAX_ITER,
+                 tol_f: float = EQ_TOL, tol_y: float = TARGET_TOL_Y):
+    """Steady states with given outputs for B scenarios on the host (no
+    device): the state and the free control inputs (columns
+    `free` of B: 0 and 2 the torques, 1 and 3 the recycle valves) at which
+    f(x, u, p) = 0 and the plant outputs `hold` equal `targets` ((nh,) or
+    (B, nh)), by Newton's method from x0 (B, ns) and u_full (B, n_inputs).
+    Returns (x, u, status, iters, resid): x and u hold the solution where
+    status is CMPC_EQ_OK and the rows given elsewhere, resid (B, 2) is
+    (max|f|, max|y - t|); the arithmetic is PlantSimulator.target's, bit for
+    bit."""
+    lib = load_library()
+    ns, ni = _plant_sizes(lib, plant)
+    h, f = _target_indices(lib, plant, hold, free, max_iter, tol_f, tol_y)
+    x = np.array(x0, dtype=np.float64, order="C")
+    B = x.shape[0] if x.ndim == 2 else 0
+    p = np.ascontiguousarray(pressures, np.float64)
+    u = np.array(u_full, dtype=np.float64, order="C")
+    if B < 1 or x.shape != (B, ns) or p.shape != (B, 2) or u.shape != (B, ni):
+        raise ValueError(f"x0 must be (B, {ns}), pressures (B, 2) and u_full (B, {ni}), "
+                         f"got {x.shape}, {p.shape} and {u.shape}")
+    t = _target_array(targets, B, len(h))
+    status, iters, resid = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros((B, 2))
+    check(lib.cmpc_plant_target_host(plant, B, dptr(p), len(h), iptr(h), iptr(f), dptr(t), dptr(u), dptr(x), max_iter,
+                                     tol_f, tol_y, iptr(status), iptr(iters), dptr(resid)), "cmpc_plant_target_host")
+    return x, u, status, iters, resid
 
 
 def _eig_iter(max_iter, n: int) -> int:
@@ -277,6 +326,41 @@ class PlantSimulator:
         check(self.lib.cmpc_sim_equilibrium_download(self._h, iptr(status), iptr(iters), dptr(resid)),
               "cmpc_sim_equilibrium_download")
         return status, iters, resid
+
+    def target(self, hold, free, targets, max_iter: int = EQ_MAX_ITER, tol_f: float = EQ_TOL,
+               tol_y: float = TARGET_TOL_Y):
+        """Move every scenario to the steady state at which its plant outputs
+        `hold` equal `targets` ((nh,) or (B, nh) host array, or a contiguous
+        float64 device tensor (B, nh)), solving for the state and the control
+        inputs `free` (plant_target has the meaning of both) from its current
+        state and plant input at the pressures in force: one launch.  Where
+        the status is CMPC_EQ_OK the state, the free entries of the plant input
+        and those of the input offset are written; a scenario with any other
+        status is left as it was, and the step sizes and the delay lines stay.
+        Returns (status, iters, resid), host arrays (B,), (B,), (B, 2)."""
+        h, f = _target_indices(self.lib, self.plant, hold, free, max_iter, tol_f, tol_y)
+        nh = len(h)
+        if isinstance(targets, self.torch.Tensor):
+            if (tuple(targets.shape) != (self.B, nh) or targets.dtype != self.torch.float64 or not targets.is_cuda
+                    or not targets.is_contiguous()):
+                raise ValueError(f"targets must be a contiguous float64 device tensor (B = {self.B}, {nh})")
+            check(self.lib.cmpc_sim_target(self._h, nh, iptr(h), iptr(f), ctypes.c_void_p(targets.data_ptr()),
+                                           max_iter, tol_f, tol_y), "cmpc_sim_target")
+        else:
+            t = _target_array(targets, self.B, nh)
+            check(self.lib.cmpc_sim_target_host(self._h, nh, iptr(h), iptr(f), dptr(t), max_iter, tol_f, tol_y),
+                  "cmpc_sim_target_host")
+        status, iters, resid = np.zeros(self.B, np.int32), np.zeros(self.B, np.int32), np.zeros((self.B, 2))
+        check(self.lib.cmpc_sim_target_download(self._h, iptr(status), iptr(iters), dptr(resid)),
+              "cmpc_sim_target_download")
+        return status, iters, resid
+
+    def download_inputs(self):
+        """Host copies: (input offset (B, n_inputs), delay line (slots, B))."""
+        off = np.zeros((self.B, self.ni))
+        ring = np.zeros((self.lib.cmpc_sim_delay_len(self._h), self.B))
+        check(self.lib.cmpc_sim_download_inputs(self._h, dptr(off), dptr(ring)), "cmpc_sim_download_inputs")
+        return off, ring
 
     def modes(self, max_iter=None):
         """The plant's modes at every scenario's current state, plant input

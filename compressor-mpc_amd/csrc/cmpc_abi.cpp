@@ -23,6 +23,7 @@
 #include "ensemble_select.h"
 #include "eig_body.h"
 #include "equilibrium_body.h"
+#include "target_body.h"
 #include "noise_body.h"
 
 namespace {
@@ -1557,6 +1558,9 @@ struct cmpc_sim {
   // results of the last cmpc_sim_equilibrium (B each, allocated on first use)
   int32_t *eq_status = nullptr, *eq_iters = nullptr;
   double* eq_resid = nullptr;
+  // results of the last cmpc_sim_target (status, iters B each, resid B * 2; allocated on first use)
+  int32_t *tg_status = nullptr, *tg_iters = nullptr;
+  double* tg_resid = nullptr;
   // results of the last cmpc_sim_modes (allocated on first use): wr, wi B * ns,
   // summary B * CMPC_MODES_NSUM, status and iters B
   double *md_wr = nullptr, *md_wi = nullptr, *md_summary = nullptr;
@@ -1624,7 +1628,7 @@ int cmpc_sim_destroy(cmpc_sim* m) {
   pinned_free(m->pin_in);
   pinned_free(m->pin_out);
   void* bufs[] = {m->x, m->dt, m->u_full, m->u_offset, m->ring, m->scratch, m->stage, m->status, m->own_pr,
-                  m->eq_status, m->eq_iters, m->eq_resid, m->md_wr, m->md_wi, m->md_summary, m->md_status,
+                  m->eq_status, m->eq_iters, m->eq_resid, m->tg_status, m->tg_iters, m->tg_resid, m->md_wr, m->md_wi, m->md_summary, m->md_status,
                   m->md_iters};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -1918,6 +1922,129 @@ int32_t* cmpc_sim_equilibrium_status(cmpc_sim* m) { return m ? m->eq_status : nu
 int32_t* cmpc_sim_equilibrium_iters(cmpc_sim* m) { return m ? m->eq_iters : nullptr; }
 double* cmpc_sim_equilibrium_resid(cmpc_sim* m) { return m ? m->eq_resid : nullptr; }
 
+// Steady-state target solve (include/cmpc.h, target_body.h, target.hip)
+int cmpc_target_check(int plant, int nh, const int32_t* hold_idx, const int32_t* free_idx, int max_iter,
+                      double tol_f, double tol_y) {
+  int ns = 0, ni = 0, no = 0, nci = 0;
+  if (cmpc_plant_dims(plant, &ns, &ni, &no, &nci)) return fail("cmpc_target_check: unknown plant");
+  if (nh < 0 || nh > cmpc_tg::kMaxHold)
+    return fail("cmpc_target_check: nh must be in [0, " + std::to_string(cmpc_tg::kMaxHold) + "]");
+  if (nh > 0 && (!hold_idx || !free_idx)) return fail("cmpc_target_check: null index array");
+  for (int j = 0; j < nh; ++j) {
+    if (hold_idx[j] < 0 || hold_idx[j] >= 4)
+      return fail("cmpc_target_check: hold_idx[" + std::to_string(j) + "] is not a plant output in [0, 4)");
+    if (free_idx[j] < 0 || free_idx[j] >= 4)
+      return fail("cmpc_target_check: free_idx[" + std::to_string(j) + "] is not a control input in [0, 4)");
+    for (int i = 0; i < j; ++i) {
+      if (hold_idx[i] == hold_idx[j])
+        return fail("cmpc_target_check: hold_idx repeats output " + std::to_string(hold_idx[j]));
+      if (free_idx[i] == free_idx[j])
+        return fail("cmpc_target_check: free_idx repeats control input " + std::to_string(free_idx[j]));
+    }
+  }
+  if (max_iter < 0 || max_iter > CMPC_EQ_MAX_ITER)
+    return fail("cmpc_target_check: max_iter must be in [0, " + std::to_string(CMPC_EQ_MAX_ITER) + "]");
+  if (!std::isfinite(tol_f) || !(tol_f > 0)) return fail("cmpc_target_check: tol_f must be finite and positive");
+  if (!std::isfinite(tol_y) || !(tol_y > 0)) return fail("cmpc_target_check: tol_y must be finite and positive");
+  return 0;
+}
+
+int cmpc_plant_target_host(int plant, int B, const double* pressures, int nh, const int32_t* hold_idx,
+                           const int32_t* free_idx, const double* targets, double* u_full, double* x, int max_iter,
+                           double tol_f, double tol_y, int32_t* status, int32_t* iters, double* resid) {
+  if (cmpc_target_check(plant, nh, hold_idx, free_idx, max_iter, tol_f, tol_y)) return -1;
+  int ns = 0, ni = 0, no = 0, nci = 0;
+  (void)cmpc_plant_dims(plant, &ns, &ni, &no, &nci);
+  if (B < 1) return fail("cmpc_plant_target_host: B must be >= 1");
+  if (!pressures || !u_full || !x || !status || !iters || !resid || (nh > 0 && !targets))
+    return fail("cmpc_plant_target_host: null argument");
+  for (size_t b = 0; b < (size_t)B; ++b) {
+    const double p_in = pressures[2 * b], p_out = pressures[2 * b + 1];
+    const double* t = nh > 0 ? targets + b * nh : nullptr;
+    status[b] = plant == CMPC_PLANT_PARALLEL
+                    ? cmpc_tg::tg_solve<CMPC_PLANT_PARALLEL>(p_in, p_out, nh, hold_idx, free_idx, t, u_full + b * ni,
+                                                             x + b * ns, max_iter, tol_f, tol_y, iters + b,
+                                                             resid + 2 * b)
+                    : cmpc_tg::tg_solve<CMPC_PLANT_SERIAL>(p_in, p_out, nh, hold_idx, free_idx, t, u_full + b * ni,
+                                                           x + b * ns, max_iter, tol_f, tol_y, iters + b,
+                                                           resid + 2 * b);
+  }
+  return 0;
+}
+
+int cmpc_sim_target(cmpc_sim* m, int nh, const int32_t* hold_idx, const int32_t* free_idx,
+                    const double* targets_device, int max_iter, double tol_f, double tol_y) {
+  if (!m) return fail("cmpc_sim_target: null simulator");
+  if (cmpc_target_check(m->plant, nh, hold_idx, free_idx, max_iter, tol_f, tol_y)) return -1;
+  if (nh > 0 && !targets_device) return fail("cmpc_sim_target: null targets");
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t Bz = (size_t)m->B;
+  if (!m->tg_status) HIP_TRY(hipMalloc(&m->tg_status, sizeof(int32_t) * Bz));
+  if (!m->tg_iters) HIP_TRY(hipMalloc(&m->tg_iters, sizeof(int32_t) * Bz));
+  if (!m->tg_resid) HIP_TRY(hipMalloc(&m->tg_resid, sizeof(double) * 2 * Bz));
+  TargetParams P;
+  std::memset(&P, 0, sizeof P);
+  P.x = m->x;
+  P.u_full = m->u_full;
+  P.u_offset = m->u_offset;
+  P.targets = nh > 0 ? targets_device : nullptr;
+  P.sim_status = m->status;
+  P.pressures = m->pr;  // the per-scenario instance reads scenario b's pair at this launch
+  P.status = m->tg_status;
+  P.iters = m->tg_iters;
+  P.resid = m->tg_resid;
+  P.B = m->B;
+  P.max_iter = max_iter;
+  P.nh = nh;
+  for (int j = 0; j < nh; ++j) {
+    P.hold[j] = hold_idx[j];
+    P.fre[j] = free_idx[j];
+  }
+  P.tol_f = tol_f;
+  P.tol_y = tol_y;
+  P.p_in = m->p_in;
+  P.p_out = m->p_out;
+  if (cmpc_launch_target(P, m->plant, m->stream)) return fail("target launch failed");
+  return check_launch("target kernel");
+}
+
+int cmpc_sim_target_host(cmpc_sim* m, int nh, const int32_t* hold_idx, const int32_t* free_idx,
+                         const double* targets, int max_iter, double tol_f, double tol_y) {
+  if (!m) return fail("cmpc_sim_target_host: null simulator");
+  if (cmpc_target_check(m->plant, nh, hold_idx, free_idx, max_iter, tol_f, tol_y)) return -1;
+  if (nh > 0 && !targets) return fail("cmpc_sim_target_host: null targets");
+  HIP_TRY(hipSetDevice(m->device));
+  // the staging buffer holds 2 * max(ns, ni, no, nc) >= nh doubles per scenario
+  if (nh > 0)
+    HIP_TRY(hipMemcpyAsync(m->stage, targets, sizeof(double) * (size_t)m->B * nh, hipMemcpyHostToDevice, m->stream));
+  const int rc = cmpc_sim_target(m, nh, hold_idx, free_idx, m->stage, max_iter, tol_f, tol_y);
+  HIP_TRY(hipStreamSynchronize(m->stream));  // (the host array is free again)
+  return rc;
+}
+
+int cmpc_sim_target_download(cmpc_sim* m, int32_t* status, int32_t* iters, double* resid) {
+  if (!m) return fail("cmpc_sim_target_download: null simulator");
+  if (!m->tg_status) return fail("cmpc_sim_target_download: call cmpc_sim_target first");
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t Bz = (size_t)m->B, bi = sizeof(int32_t) * Bz, br = sizeof(double) * 2 * Bz;
+  auto up = [](size_t v) { return (v + 15) / 16 * 16; };
+  const size_t oi = up(br), os = oi + up(bi);
+  if (pinned_acquire(m->pin_out, os + bi)) return -1;
+  char* h = m->pin_out.buf;
+  if (resid) HIP_TRY(hipMemcpyAsync(h, m->tg_resid, br, hipMemcpyDeviceToHost, m->stream));
+  if (iters) HIP_TRY(hipMemcpyAsync(h + oi, m->tg_iters, bi, hipMemcpyDeviceToHost, m->stream));
+  if (status) HIP_TRY(hipMemcpyAsync(h + os, m->tg_status, bi, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  if (resid) std::memcpy(resid, h, br);
+  if (iters) std::memcpy(iters, h + oi, bi);
+  if (status) std::memcpy(status, h + os, bi);
+  return 0;
+}
+
+int32_t* cmpc_sim_target_status(cmpc_sim* m) { return m ? m->tg_status : nullptr; }
+int32_t* cmpc_sim_target_iters(cmpc_sim* m) { return m ? m->tg_iters : nullptr; }
+double* cmpc_sim_target_resid(cmpc_sim* m) { return m ? m->tg_resid : nullptr; }
+
 // Eigenvalues and plant modes (include/cmpc.h, eig_body.h, eig.hip)
 static int eig_check(const char* who, int max_iter) {
   if (max_iter < 1 || max_iter > CMPC_EIG_MAX_ITER)
@@ -2141,6 +2268,17 @@ double* cmpc_sim_state(cmpc_sim* m) { return m ? m->x : nullptr; }
 double* cmpc_sim_input(cmpc_sim* m) { return m ? m->u_full : nullptr; }
 double* cmpc_sim_step_size(cmpc_sim* m) { return m ? m->dt : nullptr; }
 int32_t* cmpc_sim_status(cmpc_sim* m) { return m ? m->status : nullptr; }
+int cmpc_sim_delay_len(cmpc_sim* m) { return m ? m->ring_len : -1; }
+
+int cmpc_sim_download_inputs(cmpc_sim* m, double* u_offset, double* delay_line) {
+  if (!m) return fail("null simulator");
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t Bz = (size_t)m->B;
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  if (u_offset) HIP_TRY(hipMemcpy(u_offset, m->u_offset, sizeof(double) * Bz * m->ni, hipMemcpyDeviceToHost));
+  if (delay_line) HIP_TRY(hipMemcpy(delay_line, m->ring, sizeof(double) * Bz * m->ring_len, hipMemcpyDeviceToHost));
+  return 0;
+}
 
 int cmpc_sim_synchronize(cmpc_sim* m) {
   if (!m) return fail("null simulator");

@@ -644,6 +644,24 @@ struct EquilibriumParams {
 };
 // four scenarios per wave; -1: unknown plant, max_iter outside [0, 64] or a null array
 int cmpc_launch_equilibrium(const EquilibriumParams& P, int plant, void* stream);
+// Steady-state target solve (target.hip, cmpc_sim_target)
+struct TargetParams {
+  double* x;                  // B * ns, in and out (written where the status is CMPC_EQ_OK)
+  double* u_full;             // B * n_inputs: the free entries written where the status is CMPC_EQ_OK
+  double* u_offset;           // B * n_inputs: likewise, moved by the same amount
+  const double* targets;      // B * nh (null when nh = 0)
+  const int32_t* sim_status;  // B or null: nonzero leaves the scenario alone (CMPC_EQ_SKIPPED)
+  const double* pressures;    // B * 2, [p_in, p_out] per scenario, 16-byte aligned; null: p_in, p_out
+  int32_t* status;            // B: CMPC_EQ_*
+  int32_t* iters;             // B
+  double* resid;              // B * 2: (r_f, r_y)
+  int B, max_iter, nh;
+  int32_t hold[4], fre[4];    // held plant outputs, free control inputs (the first nh of each)
+  double tol_f, tol_y, p_in, p_out;
+};
+// four scenarios per wave; -1: unknown plant, max_iter outside [0, 64], nh
+// outside [0, 4], an index outside [0, 4) or a null array
+int cmpc_launch_target(const TargetParams& P, int plant, void* stream);
 // Eigenvalues and plant modes (eig.hip, cmpc_eig_device, cmpc_sim_modes)
 struct EigParams {
   const double* A;   // B * n * n, row-major blocks

@@ -1227,6 +1227,72 @@ int cmpc_sim_equilibrium_download(cmpc_sim* sim, int32_t* status, int32_t* iters
 int32_t* cmpc_sim_equilibrium_status(cmpc_sim* sim);
 int32_t* cmpc_sim_equilibrium_iters(cmpc_sim* sim);
 double* cmpc_sim_equilibrium_resid(cmpc_sim* sim);
+/* Steady-state targets: for each scenario the state x and
+ * nh <= 4 free control inputs with f(x, u, p) = 0 and y_h(x) = t_h for nh held
+ * plant outputs, by Newton's method from the x and u given; the inputs that
+ * are not free stay.  hold_idx[nh]: distinct plant outputs in [0, 4).
+ * free_idx[nh]: distinct control inputs in [0, 4), the columns of the
+ * continuous B in plant order (plant inputs 0, 3, 4, 7 of both plants: 0 and 2
+ * are the torques, 1 and 3 the recycle valves).  targets: B x nh, in plant-
+ * output units.  Each iteration linearises the plant (A, B, C and f as
+ * cmpc_plant_lin_record does before it discretises), takes r_f = max|f_i| and
+ * r_y = max|y_h - t_h| and solves
+ *   [[A, B_free], [C_hold, 0]] d = [-f; t - y]
+ * by the equilibrium solve's elimination on ns + 4 rows, an unused border row
+ * and column being the unit ones; host and device run the same arithmetic
+ * (csrc/target_body.h) and agree bit for bit, and nh = 0 is the equilibrium
+ * solve bit for bit.  The torque columns of B and C are exact derivatives, and
+ * so is a recycle column from u_rec >= 2e-2; below that the plant's recycle
+ * flow jumps (at 1e-2) and the column is an approximation, so a scenario with
+ * a free recycle valve below 2e-2, on entry or after a Newton step, stops:
+ *   CMPC_EQ_DEADZONE        a free recycle valve below 2e-2: not iterated
+ * The other statuses are the equilibrium solve's (OK: r_f <= tol_f and r_y <=
+ * tol_y; NONFINITE: an entry of the bordered system; SKIPPED: the simulator's
+ * status was nonzero).  Every status but CMPC_EQ_OK leaves x, the plant input
+ * and the offset as they were; iters is the iteration that returned, resid
+ * the pair (r_f, r_y) of its last test (B x 2).  max_iter in [0, 64], both
+ * tolerances finite and > 0; 20, 1e-12 and 1e-10 are the Python layer's.
+ *   cmpc_target_check       -1 with a message for an unknown plant, nh outside
+ *                           [0, 4], a repeated or out-of-range index, max_iter
+ *                           outside [0, 64] or a bad tolerance (host only)
+ *   cmpc_plant_target_host  B scenarios on the host, no device: u_full
+ *                           B x n_inputs and x B x ns in and out
+ *   cmpc_sim_target         the simulator's scenarios on its stream, one
+ *                           launch, from its current x and plant input at the
+ *                           pressures in force; targets a device array.  Where
+ *                           the status is CMPC_EQ_OK it writes x, the free
+ *                           entries v of the plant input, and the same entries
+ *                           of the input offset as v - (u_full - u_offset) of
+ *                           before: exactly v when no control input is in the
+ *                           delay line.  The step sizes and the delay lines
+ *                           stay as they are
+ *   cmpc_sim_target_host    the same with targets on the host; synchronises
+ *   cmpc_sim_target_download  host copies of the last solve's results (any
+ *                           pointer may be NULL; resid B x 2); synchronises
+ *   cmpc_sim_target_status, _iters, _resid  the device arrays (NULL before the
+ *                           first cmpc_sim_target); buffers of their own:
+ *                           cmpc_sim_equilibrium_download keeps its meaning
+ *   cmpc_sim_download_inputs  host copies of the simulator's input offset
+ *                           (B x n_inputs) and of its delay line
+ *                           (cmpc_sim_delay_len slots of B doubles); either
+ *                           pointer may be NULL; synchronises */
+#define CMPC_EQ_DEADZONE 5
+int cmpc_target_check(int plant, int nh, const int32_t* hold_idx, const int32_t* free_idx, int max_iter,
+                      double tol_f, double tol_y);
+int cmpc_plant_target_host(int plant, int B, const double* pressures /* B*2 */, int nh, const int32_t* hold_idx,
+                           const int32_t* free_idx, const double* targets /* B*nh */,
+                           double* u_full /* B*n_inputs, in/out */, double* x /* B*ns, in/out */, int max_iter,
+                           double tol_f, double tol_y, int32_t* status, int32_t* iters, double* resid /* B*2 */);
+int cmpc_sim_target(cmpc_sim* sim, int nh, const int32_t* hold_idx, const int32_t* free_idx,
+                    const double* targets_device /* B*nh */, int max_iter, double tol_f, double tol_y);
+int cmpc_sim_target_host(cmpc_sim* sim, int nh, const int32_t* hold_idx, const int32_t* free_idx,
+                         const double* targets /* B*nh, host */, int max_iter, double tol_f, double tol_y);
+int cmpc_sim_target_download(cmpc_sim* sim, int32_t* status, int32_t* iters, double* resid /* B*2 */);
+int32_t* cmpc_sim_target_status(cmpc_sim* sim);
+int32_t* cmpc_sim_target_iters(cmpc_sim* sim);
+double* cmpc_sim_target_resid(cmpc_sim* sim);
+int cmpc_sim_delay_len(cmpc_sim* sim);
+int cmpc_sim_download_inputs(cmpc_sim* sim, double* u_offset /* B*n_inputs */, double* delay_line);
 /* Plant modes: the eigenvalues of small real nonsymmetric
  * matrices in batches, and on top of them the modes of the plant, that is the
  * eigenvalues of the continuous Jacobian A = df/dx at each scenario's state
