@@ -171,6 +171,8 @@ EXPORTS = (
     "cmpc_target_check", "cmpc_plant_target_host", "cmpc_sim_target", "cmpc_sim_target_host",
     "cmpc_sim_target_download", "cmpc_sim_target_status", "cmpc_sim_target_iters", "cmpc_sim_target_resid",
     "cmpc_sim_delay_len", "cmpc_sim_download_inputs",
+    "cmpc_gain_check", "cmpc_plant_gains_host", "cmpc_sim_gains", "cmpc_sim_gains_download",
+    "cmpc_sim_gains_record", "cmpc_sim_gains_status",
     "cmpc_eig_host", "cmpc_eig_device", "cmpc_modes_summary_host", "cmpc_plant_modes_host", "cmpc_sim_modes",
     "cmpc_sim_modes_download", "cmpc_sim_modes_wr", "cmpc_sim_modes_wi", "cmpc_sim_modes_summary",
     "cmpc_sim_modes_status", "cmpc_sim_modes_iters",
@@ -183,6 +185,8 @@ CMPC_EQ_NONFINITE = 2
 CMPC_EQ_SINGULAR = 3
 CMPC_EQ_SKIPPED = 4
 CMPC_EQ_DEADZONE = 5   # the target solve only: a free recycle valve below 2e-2
+CMPC_GAIN_SINGULAR_G = 6   # the gains only: G of a square selection has no inverse
+CMPC_GAIN_LEN = 49         # doubles per gains record: G 4x4, Gp 4x2, RGA 4x4, K_ff 4x2, r_f
 CMPC_EQ_MAX_ITER = 64
 
 # per-matrix statuses of the eigenvalue solver and the summary of the plant
@@ -449,6 +453,13 @@ def load_library(path: str = LIB_PATH):
         "cmpc_sim_target_resid": ([c_void], c_void),
         "cmpc_sim_delay_len": ([c_void], ctypes.c_int),
         "cmpc_sim_download_inputs": ([c_void, P(dbl), P(dbl)], ctypes.c_int),
+        "cmpc_gain_check": ([ctypes.c_int, ctypes.c_int, P(i32), ctypes.c_int, P(i32)], ctypes.c_int),
+        "cmpc_plant_gains_host": ([ctypes.c_int, ctypes.c_int, P(dbl), P(dbl), P(dbl), ctypes.c_int, P(i32),
+                                   ctypes.c_int, P(i32), P(dbl), P(i32)], ctypes.c_int),
+        "cmpc_sim_gains": ([c_void, ctypes.c_int, P(i32), ctypes.c_int, P(i32)], ctypes.c_int),
+        "cmpc_sim_gains_download": ([c_void, P(dbl), P(i32)], ctypes.c_int),
+        "cmpc_sim_gains_record": ([c_void], c_void),
+        "cmpc_sim_gains_status": ([c_void], c_void),
         "cmpc_eig_host": ([ctypes.c_int, ctypes.c_int, P(dbl), ctypes.c_int, P(dbl), P(dbl), P(i32), P(i32)],
                           ctypes.c_int),
         "cmpc_eig_device": ([ctypes.c_int, ctypes.c_int, c_void, ctypes.c_int, c_void, c_void, c_void, c_void,

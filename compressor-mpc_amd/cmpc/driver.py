@@ -36,7 +36,7 @@ import numpy as np
 from . import CMPC_TRACE, Context, scenario_limits, scenario_reference_offsets
 from .configs import ControllerConfig
 from .sim import (EQ_MAX_ITER, EQ_TOL, REF_CONTROL_INDEX, REF_DELAYS, REF_EPS, REF_TS, TARGET_TOL_Y,
-                  PlantSimulator)
+                  PlantGains, PlantSimulator)  # noqa: F401
 
 # ClosedLoop.modes: the summary's columns (include/cmpc.h, _abi.MODES_SUMMARY),
 # the eigenvalues and the statuses
@@ -558,6 +558,17 @@ class ClosedLoop:
         w, sm, status, _ = self.sim.modes(max_iter)
         return PlantModes(sm[:, 0].copy(), sm[:, 1].copy(), sm[:, 2].copy(), sm[:, 3].copy(), sm[:, 4].copy(),
                           sm[:, 5].copy(), w, status)
+
+    def gains(self, outputs, inputs=(0, 2)) -> "PlantGains":
+        """The plant's steady-state gains at the loop's current states (after
+        trim or trim_to_outputs), under the plant pressures in force
+        (PlantSimulator.gains, one launch; nothing of the loop is written;
+        DESIGN.md §3.22): a PlantGains record of G (B, ny, nu) = dy/du from
+        the control inputs `inputs` to the plant outputs `outputs`, Gp
+        (B, ny, 2) = dy/d(p_in, p_out), and for ny == nu the relative gain
+        array rga and the pressure feed-forward k_ff (B, n, 2), with resid
+        (B,) = max|f| and status (B,)."""
+        return self.sim.gains(outputs, inputs)
 
     def initialize(self, dx_init=None):
         """SimulationSystem(x0, u_offset) + NerveCenter::Initialize(x0, 0,

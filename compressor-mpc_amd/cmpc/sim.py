@@ -4,11 +4,12 @@ scenarios: input delay line (TimeDelay, time_delay.h:41-58), controlled
 Dormand-Prince over one sampling interval per call (integrate_const,
 simulation_system.h:108-116), plant outputs.  Arrays are torch tensors on
 the device (plumbing: the simulation itself is the HIP kernel in sim.hip)."""
+import collections
 import ctypes
 
 import numpy as np
 
-from ._abi import CMPC_EIG_MAX_N, CMPC_MODES_NSUM, check, dptr, iptr, load_library
+from ._abi import CMPC_EIG_MAX_N, CMPC_GAIN_LEN, CMPC_MODES_NSUM, check, dptr, iptr, load_library
 
 REF_DELAYS = (0, 40, 0, 40)          # Delays of both plants (control-input order)
 REF_CONTROL_INDEX = (0, 3, 4, 7)     # ControlInputIndex: plant input of each control input
@@ -105,6 +106,58 @@ def plant_target(plant: int, pressures, hold, free, targets, u_full, x0, max_ite
     check(lib.cmpc_plant_target_host(plant, B, dptr(p), len(h), iptr(h), iptr(f), dptr(t), dptr(u), dptr(x), max_iter,
                                      tol_f, tol_y, iptr(status), iptr(iters), dptr(resid)), "cmpc_plant_target_host")
     return x, u, status, iters, resid
+
+
+# plant_gains, PlantSimulator.gains, ClosedLoop.gains: the record of
+# include/cmpc.h sliced to the selection, and the raw record (B, CMPC_GAIN_LEN)
+PlantGains = collections.namedtuple("PlantGains", ("G", "Gp", "rga", "k_ff", "resid", "status", "record"))
+
+
+def _gain_indices(lib, plant: int, outputs, inputs):
+    """outputs and inputs as int32 arrays, checked by cmpc_gain_check."""
+    o = np.ascontiguousarray(outputs, np.int32).reshape(-1)
+    i = np.ascontiguousarray(inputs, np.int32).reshape(-1)
+    check(lib.cmpc_gain_check(plant, len(o), iptr(o), len(i), iptr(i)), "cmpc_gain_check")
+    return o, i
+
+
+def _gain_result(record, status, ny: int, nu: int) -> "PlantGains":
+    """The record's blocks, sliced to ny and nu (views of the record)."""
+    B = record.shape[0]
+    return PlantGains(G=record[:, 0:16].reshape(B, 4, 4)[:, :ny, :nu],
+                      Gp=record[:, 16:24].reshape(B, 4, 2)[:, :ny],
+                      rga=record[:, 24:40].reshape(B, 4, 4)[:, :ny, :nu],
+                      k_ff=record[:, 40:48].reshape(B, 4, 2)[:, :nu],
+                      resid=record[:, 48], status=status, record=record)
+
+
+def plant_gains(plant: int, pressures, u_full, x, outputs, inputs=(0, 2)) -> "PlantGains":
+    """Steady-state gains for B scenarios on the host (no device, DESIGN.md
+    §3.22): at x (B, ns), u_full (B, n_inputs) and pressures (B, 2), the map
+    from the control inputs `inputs` (columns of B: 0 and 2 the torques, 1
+    and 3 the recycle valves) and from (p_in, p_out) to the plant outputs
+    `outputs`.  Returns a PlantGains record: G (B, ny, nu) = dy/du, Gp
+    (B, ny, 2) = dy/dp, and for ny == nu the relative gain array rga
+    (B, n, n) and the feed-forward k_ff (B, n, 2) = du/dp that holds the
+    outputs (NaN otherwise), resid (B,) = max|f| at x (the gains are
+    steady-state gains where it is ~ 0), status (B,) and the raw record
+    (B, CMPC_GAIN_LEN); everything is NaN where status is neither CMPC_EQ_OK
+    nor CMPC_GAIN_SINGULAR_G.  The arithmetic is PlantSimulator.gains', bit
+    for bit."""
+    lib = load_library()
+    ns, ni = _plant_sizes(lib, plant)
+    o, i = _gain_indices(lib, plant, outputs, inputs)
+    xs = np.ascontiguousarray(x, np.float64)
+    B = xs.shape[0] if xs.ndim == 2 else 0
+    p = np.ascontiguousarray(pressures, np.float64)
+    u = np.ascontiguousarray(u_full, np.float64)
+    if B < 1 or xs.shape != (B, ns) or p.shape != (B, 2) or u.shape != (B, ni):
+        raise ValueError(f"x must be (B, {ns}), pressures (B, 2) and u_full (B, {ni}), "
+                         f"got {xs.shape}, {p.shape} and {u.shape}")
+    record, status = np.zeros((B, CMPC_GAIN_LEN)), np.zeros(B, np.int32)
+    check(lib.cmpc_plant_gains_host(plant, B, dptr(p), dptr(u), dptr(xs), len(o), iptr(o), len(i), iptr(i),
+                                    dptr(record), iptr(status)), "cmpc_plant_gains_host")
+    return _gain_result(record, status, len(o), len(i))
 
 
 def _eig_iter(max_iter, n: int) -> int:
@@ -361,6 +414,18 @@ class PlantSimulator:
         ring = np.zeros((self.lib.cmpc_sim_delay_len(self._h), self.B))
         check(self.lib.cmpc_sim_download_inputs(self._h, dptr(off), dptr(ring)), "cmpc_sim_download_inputs")
         return off, ring
+
+    def gains(self, outputs, inputs=(0, 2)) -> "PlantGains":
+        """The steady-state gains, relative gain array and pressure
+        feed-forward at every scenario's current state, plant input and the
+        pressures in force (one launch; nothing of the simulator is written).
+        Returns what plant_gains returns, bit for bit; a scenario whose
+        simulator status is nonzero reports CMPC_EQ_SKIPPED with NaN."""
+        o, i = _gain_indices(self.lib, self.plant, outputs, inputs)
+        check(self.lib.cmpc_sim_gains(self._h, len(o), iptr(o), len(i), iptr(i)), "cmpc_sim_gains")
+        record, status = np.zeros((self.B, CMPC_GAIN_LEN)), np.zeros(self.B, np.int32)
+        check(self.lib.cmpc_sim_gains_download(self._h, dptr(record), iptr(status)), "cmpc_sim_gains_download")
+        return _gain_result(record, status, len(o), len(i))
 
     def modes(self, max_iter=None):
         """The plant's modes at every scenario's current state, plant input

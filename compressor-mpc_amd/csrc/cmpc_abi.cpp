@@ -24,6 +24,7 @@
 #include "eig_body.h"
 #include "equilibrium_body.h"
 #include "target_body.h"
+#include "gains_body.h"
 #include "noise_body.h"
 
 namespace {
@@ -1561,6 +1562,9 @@ struct cmpc_sim {
   // results of the last cmpc_sim_target (status, iters B each, resid B * 2; allocated on first use)
   int32_t *tg_status = nullptr, *tg_iters = nullptr;
   double* tg_resid = nullptr;
+  // results of the last cmpc_sim_gains (record B * CMPC_GAIN_LEN, status B; allocated on first use)
+  double* gn_record = nullptr;
+  int32_t* gn_status = nullptr;
   // results of the last cmpc_sim_modes (allocated on first use): wr, wi B * ns,
   // summary B * CMPC_MODES_NSUM, status and iters B
   double *md_wr = nullptr, *md_wi = nullptr, *md_summary = nullptr;
@@ -1628,7 +1632,7 @@ int cmpc_sim_destroy(cmpc_sim* m) {
   pinned_free(m->pin_in);
   pinned_free(m->pin_out);
   void* bufs[] = {m->x, m->dt, m->u_full, m->u_offset, m->ring, m->scratch, m->stage, m->status, m->own_pr,
-                  m->eq_status, m->eq_iters, m->eq_resid, m->tg_status, m->tg_iters, m->tg_resid, m->md_wr, m->md_wi, m->md_summary, m->md_status,
+                  m->eq_status, m->eq_iters, m->eq_resid, m->tg_status, m->tg_iters, m->tg_resid, m->gn_record, m->gn_status, m->md_wr, m->md_wi, m->md_summary, m->md_status,
                   m->md_iters};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
@@ -2044,6 +2048,97 @@ int cmpc_sim_target_download(cmpc_sim* m, int32_t* status, int32_t* iters, doubl
 int32_t* cmpc_sim_target_status(cmpc_sim* m) { return m ? m->tg_status : nullptr; }
 int32_t* cmpc_sim_target_iters(cmpc_sim* m) { return m ? m->tg_iters : nullptr; }
 double* cmpc_sim_target_resid(cmpc_sim* m) { return m ? m->tg_resid : nullptr; }
+
+// Steady-state gains, RGA and pressure feed-forward (include/cmpc.h, gains_body.h, gains.hip)
+int cmpc_gain_check(int plant, int ny, const int32_t* out_idx, int nu, const int32_t* in_idx) {
+  int ns = 0, ni = 0, no = 0, nci = 0;
+  if (cmpc_plant_dims(plant, &ns, &ni, &no, &nci)) return fail("cmpc_gain_check: unknown plant");
+  if (ny < 1 || ny > cmpc_gn::kMaxSel)
+    return fail("cmpc_gain_check: ny must be in [1, " + std::to_string(cmpc_gn::kMaxSel) + "]");
+  if (nu < 1 || nu > cmpc_gn::kMaxSel)
+    return fail("cmpc_gain_check: nu must be in [1, " + std::to_string(cmpc_gn::kMaxSel) + "]");
+  if (!out_idx || !in_idx) return fail("cmpc_gain_check: null index array");
+  for (int j = 0; j < ny; ++j) {
+    if (out_idx[j] < 0 || out_idx[j] >= 4)
+      return fail("cmpc_gain_check: out_idx[" + std::to_string(j) + "] is not a plant output in [0, 4)");
+    for (int i = 0; i < j; ++i)
+      if (out_idx[i] == out_idx[j])
+        return fail("cmpc_gain_check: out_idx repeats output " + std::to_string(out_idx[j]));
+  }
+  for (int j = 0; j < nu; ++j) {
+    if (in_idx[j] < 0 || in_idx[j] >= 4)
+      return fail("cmpc_gain_check: in_idx[" + std::to_string(j) + "] is not a control input in [0, 4)");
+    for (int i = 0; i < j; ++i)
+      if (in_idx[i] == in_idx[j])
+        return fail("cmpc_gain_check: in_idx repeats control input " + std::to_string(in_idx[j]));
+  }
+  return 0;
+}
+
+int cmpc_plant_gains_host(int plant, int B, const double* pressures, const double* u_full, const double* x, int ny,
+                          const int32_t* out_idx, int nu, const int32_t* in_idx, double* record, int32_t* status) {
+  if (cmpc_gain_check(plant, ny, out_idx, nu, in_idx)) return -1;
+  int ns = 0, ni = 0, no = 0, nci = 0;
+  (void)cmpc_plant_dims(plant, &ns, &ni, &no, &nci);
+  if (B < 1) return fail("cmpc_plant_gains_host: B must be >= 1");
+  if (!pressures || !u_full || !x || !record || !status) return fail("cmpc_plant_gains_host: null argument");
+  for (size_t b = 0; b < (size_t)B; ++b) {
+    const double p_in = pressures[2 * b], p_out = pressures[2 * b + 1];
+    double* rec = record + b * CMPC_GAIN_LEN;
+    status[b] = plant == CMPC_PLANT_PARALLEL
+                    ? cmpc_gn::gn_solve<CMPC_PLANT_PARALLEL>(p_in, p_out, ny, out_idx, nu, in_idx, u_full + b * ni,
+                                                             x + b * ns, rec)
+                    : cmpc_gn::gn_solve<CMPC_PLANT_SERIAL>(p_in, p_out, ny, out_idx, nu, in_idx, u_full + b * ni,
+                                                           x + b * ns, rec);
+  }
+  return 0;
+}
+
+int cmpc_sim_gains(cmpc_sim* m, int ny, const int32_t* out_idx, int nu, const int32_t* in_idx) {
+  if (!m) return fail("cmpc_sim_gains: null simulator");
+  if (cmpc_gain_check(m->plant, ny, out_idx, nu, in_idx)) return -1;
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t Bz = (size_t)m->B;
+  if (!m->gn_record) HIP_TRY(hipMalloc(&m->gn_record, sizeof(double) * CMPC_GAIN_LEN * Bz));
+  if (!m->gn_status) HIP_TRY(hipMalloc(&m->gn_status, sizeof(int32_t) * Bz));
+  GainsParams P;
+  std::memset(&P, 0, sizeof P);
+  P.x = m->x;
+  P.u_full = m->u_full;
+  P.sim_status = m->status;
+  P.pressures = m->pr;  // the per-scenario instance reads scenario b's pair at this launch
+  P.record = m->gn_record;
+  P.status = m->gn_status;
+  P.B = m->B;
+  P.ny = ny;
+  P.nu = nu;
+  for (int j = 0; j < ny; ++j) P.out[j] = out_idx[j];
+  for (int j = 0; j < nu; ++j) P.in[j] = in_idx[j];
+  P.p_in = m->p_in;
+  P.p_out = m->p_out;
+  if (cmpc_launch_gains(P, m->plant, m->stream)) return fail("gains launch failed");
+  return check_launch("gains kernel");
+}
+
+int cmpc_sim_gains_download(cmpc_sim* m, double* record, int32_t* status) {
+  if (!m) return fail("cmpc_sim_gains_download: null simulator");
+  if (!m->gn_status) return fail("cmpc_sim_gains_download: call cmpc_sim_gains first");
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t Bz = (size_t)m->B, br = sizeof(double) * CMPC_GAIN_LEN * Bz, bi = sizeof(int32_t) * Bz;
+  auto up = [](size_t v) { return (v + 15) / 16 * 16; };
+  const size_t os = up(br);
+  if (pinned_acquire(m->pin_out, os + bi)) return -1;
+  char* h = m->pin_out.buf;
+  if (record) HIP_TRY(hipMemcpyAsync(h, m->gn_record, br, hipMemcpyDeviceToHost, m->stream));
+  if (status) HIP_TRY(hipMemcpyAsync(h + os, m->gn_status, bi, hipMemcpyDeviceToHost, m->stream));
+  HIP_TRY(hipStreamSynchronize(m->stream));
+  if (record) std::memcpy(record, h, br);
+  if (status) std::memcpy(status, h + os, bi);
+  return 0;
+}
+
+double* cmpc_sim_gains_record(cmpc_sim* m) { return m ? m->gn_record : nullptr; }
+int32_t* cmpc_sim_gains_status(cmpc_sim* m) { return m ? m->gn_status : nullptr; }
 
 // Eigenvalues and plant modes (include/cmpc.h, eig_body.h, eig.hip)
 static int eig_check(const char* who, int max_iter) {

@@ -662,6 +662,21 @@ struct TargetParams {
 // four scenarios per wave; -1: unknown plant, max_iter outside [0, 64], nh
 // outside [0, 4], an index outside [0, 4) or a null array
 int cmpc_launch_target(const TargetParams& P, int plant, void* stream);
+// Steady-state gains, RGA and pressure feed-forward (gains.hip, cmpc_sim_gains)
+struct GainsParams {
+  const double* x;            // B * ns, read only
+  const double* u_full;       // B * n_inputs, read only
+  const int32_t* sim_status;  // B or null: nonzero gives CMPC_EQ_SKIPPED
+  const double* pressures;    // B * 2, [p_in, p_out] per scenario, 16-byte aligned; null: p_in, p_out
+  double* record;             // B * CMPC_GAIN_LEN
+  int32_t* status;            // B: CMPC_EQ_* or CMPC_GAIN_SINGULAR_G
+  int B, ny, nu;
+  int32_t out[4], in[4];      // selected plant outputs and control inputs (the first ny and nu)
+  double p_in, p_out;
+};
+// four scenarios per wave; -1: unknown plant, ny or nu outside [1, 4], an index
+// outside [0, 4) or a null array
+int cmpc_launch_gains(const GainsParams& P, int plant, void* stream);
 // Eigenvalues and plant modes (eig.hip, cmpc_eig_device, cmpc_sim_modes)
 struct EigParams {
   const double* A;   // B * n * n, row-major blocks

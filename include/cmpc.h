@@ -1293,6 +1293,65 @@ int32_t* cmpc_sim_target_iters(cmpc_sim* sim);
 double* cmpc_sim_target_resid(cmpc_sim* sim);
 int cmpc_sim_delay_len(cmpc_sim* sim);
 int cmpc_sim_download_inputs(cmpc_sim* sim, double* u_offset /* B*n_inputs */, double* delay_line);
+/* Steady-state gains, relative gain array and pressure feed-forward (DESIGN.md
+ * §3.22): for each scenario the steady-state map of its linearisation at
+ * (x, u, p), from nu <= 4 control inputs and from the two boundary pressures
+ * to ny <= 4 plant outputs.  out_idx[ny]: distinct plant outputs in [0, 4),
+ * ny >= 1.  in_idx[nu]: distinct control inputs in [0, 4), nu >= 1, the
+ * columns of the continuous B as cmpc_sim_target's free_idx (0 and 2 are the
+ * torques, 1 and 3 the recycle valves).  With A, B, C, f of the continuous
+ * linearisation and E = df/dp (ns x 2) by a central difference of the plant's
+ * derivative in p_in and in p_out, step 2^-21:
+ *   G   = -C_sel A^-1 B_sel   ny x nu   d y / d u at rest
+ *   Gp  = -C_sel A^-1 E       ny x 2    d y / d (p_in, p_out) at rest
+ * through one adjoint solve A^T Z = C_sel^T by the equilibrium solve's
+ * elimination on ns rows and ns + 4 columns, and for ny == nu = n
+ *   RGA  = G .* (G^-1)^T      n x n     the relative gain array
+ *   K_ff = -G^-1 Gp           n x 2     d u / d p that holds the outputs
+ * by the same elimination on 4 rows, rows and columns from n on being the unit
+ * ones.  Host and device run the same arithmetic (csrc/gains_body.h) and agree
+ * bit for bit.  r_f = max|f_i| is reported and not tested: any state gives
+ * the gains of its linearisation, and they are steady-state gains where
+ * r_f ~ 0 (after cmpc_sim_equilibrium or cmpc_sim_target).
+ * The record, CMPC_GAIN_LEN = 49 doubles per scenario: G 4 x 4 row-major in
+ * the order of out_idx x in_idx, Gp 4 x 2, RGA 4 x 4, K_ff 4 x 2, r_f.  An
+ * entry outside ny / nu is the quiet NaN 0x7ff8000000000000.  Statuses:
+ *   CMPC_EQ_OK              with ny != nu, RGA and K_ff are that NaN
+ *   CMPC_GAIN_SINGULAR_G    ny == nu and a zero or non-finite pivot of G: G,
+ *                           Gp and r_f stand, RGA and K_ff are that NaN
+ *   CMPC_EQ_DEADZONE        a selected recycle valve below 2e-2, where its B
+ *                           column is an approximation (an unselected valve
+ *                           may stand anywhere)
+ *   CMPC_EQ_NONFINITE       an entry of A, of the selected part of B or C, of
+ *                           f or of E is not finite
+ *   CMPC_EQ_SINGULAR        a zero or non-finite pivot of A
+ *   CMPC_EQ_SKIPPED         the simulator's status was nonzero
+ * and for the last four all 49 entries are that NaN.  No status is an error
+ * of the call.
+ *   cmpc_gain_check         -1 with a message for an unknown plant, ny or nu
+ *                           outside [1, 4], a null index array, or a repeated
+ *                           or out-of-range index (host only)
+ *   cmpc_plant_gains_host   B scenarios on the host, no device: record
+ *                           B x 49, status B
+ *   cmpc_sim_gains          the simulator's scenarios on its stream, one
+ *                           launch, at its current x and plant input and the
+ *                           pressures in force (scalar, set or bound).  Nothing
+ *                           of the simulator is written: x, inputs, offset,
+ *                           step sizes and delay lines stay bit for bit
+ *   cmpc_sim_gains_download host copies of the last call's results (either
+ *                           pointer may be NULL); synchronises
+ *   cmpc_sim_gains_record, _status  the device arrays (NULL before the first
+ *                           cmpc_sim_gains); buffers of their own */
+#define CMPC_GAIN_SINGULAR_G 6
+#define CMPC_GAIN_LEN 49
+int cmpc_gain_check(int plant, int ny, const int32_t* out_idx, int nu, const int32_t* in_idx);
+int cmpc_plant_gains_host(int plant, int B, const double* pressures /* B*2 */, const double* u_full /* B*n_inputs */,
+                          const double* x /* B*ns */, int ny, const int32_t* out_idx, int nu, const int32_t* in_idx,
+                          double* record /* B*49 */, int32_t* status /* B */);
+int cmpc_sim_gains(cmpc_sim* sim, int ny, const int32_t* out_idx, int nu, const int32_t* in_idx);
+int cmpc_sim_gains_download(cmpc_sim* sim, double* record /* B*49 */, int32_t* status /* B */);
+double* cmpc_sim_gains_record(cmpc_sim* sim);
+int32_t* cmpc_sim_gains_status(cmpc_sim* sim);
 /* Plant modes: the eigenvalues of small real nonsymmetric
  * matrices in batches, and on top of them the modes of the plant, that is the
  * eigenvalues of the continuous Jacobian A = df/dx at each scenario's state
