@@ -190,7 +190,7 @@
 // raw references in global memory (the same rows for every QP of a wave, so
 // cache hits; a block-shared copy costs the LDS of a fourth workgroup per CU
 // at the bench shape), in the host's arithmetic order (rebuild_cfg,
-// cmpc_abi.cpp); yl, lwt and uwt point at the private copies and nothing else
+// abi_ctx.cpp); yl, lwt and uwt point at the private copies and nothing else
 // changes, so a slot whose block equals sub-controller s's shared one gets the
 // bit-identical QP.
 template <int NS, int NY, int NUT, int NU, int M, int ND, int FUSE, bool SPLIT = false, int SW = 2,

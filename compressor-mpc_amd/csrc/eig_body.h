@@ -1,7 +1,7 @@
 // Eigenvalues of a small real nonsymmetric matrix (cmpc_eig_host,
 // cmpc_eig_device, cmpc_plant_modes_host, cmpc_sim_modes):
 // the arithmetic of one N x N matrix, N <= 12, no eigenvectors, shared by the
-// host entry points (cmpc_abi.cpp) and the device kernels (eig.hip).
+// host entry points (abi_analysis.cpp) and the device kernels (eig.hip).
 //
 // One text serves both sides.  The work of a stage is written per "lane": lane
 // j owns column j where a transformation multiplies from the left and row j

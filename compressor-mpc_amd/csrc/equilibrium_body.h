@@ -1,6 +1,6 @@
 // Plant equilibrium by Newton's method (cmpc_plant_equilibrium_host,
 // cmpc_sim_equilibrium): the arithmetic of one scenario,
-// shared by the host entry point (cmpc_abi.cpp) and the device kernel
+// shared by the host entry point (abi_analysis.cpp) and the device kernel
 // (equilibrium.hip).  Given the plant input u and the boundary pressures, find
 // x with f(x, u, p) = 0, starting from the x given.
 //

@@ -1,6 +1,6 @@
 // Steady-state gains, relative gain array and pressure feed-forward
 // (cmpc_plant_gains_host, cmpc_sim_gains): the arithmetic of
-// one scenario, shared by the host entry point (cmpc_abi.cpp) and the device
+// one scenario, shared by the host entry point (abi_analysis.cpp) and the device
 // kernel (gains.hip).  Given the state x, the plant input u and the boundary
 // pressures p, ny plant outputs out[] and nu control inputs in[] (columns of
 // the continuous B, as the target solve's free inputs):

@@ -1,5 +1,5 @@
 // Seeded per-scenario noise (cmpc_noise_*): the arithmetic of
-// one draw, shared by the host entry points (cmpc_abi.cpp) and the device
+// one draw, shared by the host entry points (abi_free.cpp) and the device
 // kernels (noise.hip).  A draw is a pure function of (seed, stream, global
 // scenario, step, channel): no generator state, no dependence on the batch
 // size or the launch shape.

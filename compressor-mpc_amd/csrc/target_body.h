@@ -1,6 +1,6 @@
 // Steady-state target solve (cmpc_plant_target_host, cmpc_sim_target,
 // DESIGN.md §3.21): the arithmetic of one scenario, shared by the host entry
-// point (cmpc_abi.cpp) and the device kernel (target.hip).  Given the boundary
+// point (abi_analysis.cpp) and the device kernel (target.hip).  Given the boundary
 // pressures, nh <= 4 held plant outputs with their targets t and as many free
 // control inputs, find the state x and the free inputs with
 //   f(x, u, p) = 0   and   y_h(x) = t_h  for the held outputs h,
