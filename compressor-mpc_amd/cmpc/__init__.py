@@ -28,11 +28,13 @@ from ._abi import (CMPC_BUILD_AUTO, CMPC_BUILD_ROWS, CMPC_BUILD_SPLIT, CMPC_BUIL
 from .configs import ControllerConfig, SetupFile, reference_config, reference_observer_gain, reference_setup
 from .problem import ControllerArrays, controller_arrays, plant_input_from_plans
 from ._abi import (CMPC_EQ_OK, CMPC_EQ_NO_CONVERGENCE, CMPC_EQ_NONFINITE, CMPC_EQ_SINGULAR,  # noqa: F401
-                   CMPC_EQ_SKIPPED, CMPC_EQ_DEADZONE, CMPC_GAIN_SINGULAR_G, CMPC_GAIN_LEN)
+                   CMPC_EQ_SKIPPED, CMPC_EQ_DEADZONE, CMPC_GAIN_SINGULAR_G, CMPC_GAIN_LEN,
+                   CMPC_FREQ_MAX_NW, CMPC_FREQ_MAX_N, CMPC_FREQ_LEN, CMPC_FREQ_NSUM)
 from ._abi import (CMPC_EIG_OK, CMPC_EIG_NO_CONVERGENCE, CMPC_EIG_NONFINITE, CMPC_EIG_SKIPPED,  # noqa: F401
                    CMPC_EIG_MAX_ITER, CMPC_MODES_NSUM)
 from .sim import plant_derivative, plant_equilibrium, plant_target  # noqa: F401
 from .sim import PlantGains, plant_gains  # noqa: F401
+from .sim import FreqResponse, freq_response, plant_freq_response  # noqa: F401
 from .sim import eig_batch, eig_batch_device, modes_summary, plant_modes  # noqa: F401
 
 __all__ = ["Context", "ControllerConfig", "SetupFile", "reference_config", "reference_setup",
@@ -52,6 +54,8 @@ __all__ = ["Context", "ControllerConfig", "SetupFile", "reference_config", "refe
            "plant_derivative", "plant_equilibrium", "CMPC_EQ_OK", "CMPC_EQ_NO_CONVERGENCE", "CMPC_EQ_NONFINITE",
            "CMPC_EQ_SINGULAR", "CMPC_EQ_SKIPPED", "CMPC_EQ_DEADZONE", "plant_target",
            "CMPC_GAIN_SINGULAR_G", "CMPC_GAIN_LEN", "PlantGains", "plant_gains",
+           "CMPC_FREQ_MAX_NW", "CMPC_FREQ_MAX_N", "CMPC_FREQ_LEN", "CMPC_FREQ_NSUM", "FreqResponse", "freq_response",
+           "plant_freq_response",
            "eig_batch", "eig_batch_device", "modes_summary", "plant_modes", "CMPC_EIG_OK", "CMPC_EIG_NO_CONVERGENCE",
            "CMPC_EIG_NONFINITE", "CMPC_EIG_SKIPPED", "CMPC_EIG_MAX_ITER", "CMPC_MODES_NSUM"]
 

@@ -173,6 +173,8 @@ EXPORTS = (
     "cmpc_sim_delay_len", "cmpc_sim_download_inputs",
     "cmpc_gain_check", "cmpc_plant_gains_host", "cmpc_sim_gains", "cmpc_sim_gains_download",
     "cmpc_sim_gains_record", "cmpc_sim_gains_status",
+    "cmpc_freq_check", "cmpc_plant_freq_host", "cmpc_freq_host", "cmpc_sim_freq", "cmpc_sim_freq_download",
+    "cmpc_sim_freq_record", "cmpc_sim_freq_summary", "cmpc_sim_freq_status",
     "cmpc_eig_host", "cmpc_eig_device", "cmpc_modes_summary_host", "cmpc_plant_modes_host", "cmpc_sim_modes",
     "cmpc_sim_modes_download", "cmpc_sim_modes_wr", "cmpc_sim_modes_wi", "cmpc_sim_modes_summary",
     "cmpc_sim_modes_status", "cmpc_sim_modes_iters",
@@ -188,6 +190,10 @@ CMPC_EQ_DEADZONE = 5   # the target solve only: a free recycle valve below 2e-2
 CMPC_GAIN_SINGULAR_G = 6   # the gains only: G of a square selection has no inverse
 CMPC_GAIN_LEN = 49         # doubles per gains record: G 4x4, Gp 4x2, RGA 4x4, K_ff 4x2, r_f
 CMPC_EQ_MAX_ITER = 64
+CMPC_FREQ_MAX_NW = 64      # frequencies per frequency-response call, at most
+CMPC_FREQ_MAX_N = 12       # the matrix-level host call's largest n
+CMPC_FREQ_LEN = 48         # doubles per scenario and frequency: G 4x4 and Gp 4x2 as (re, im) pairs
+CMPC_FREQ_NSUM = 49        # doubles per scenario: 24 peaks of re^2 + im^2, their 24 indices, r_f
 
 # per-matrix statuses of the eigenvalue solver and the summary of the plant
 # modes (include/cmpc.h)
@@ -460,6 +466,17 @@ def load_library(path: str = LIB_PATH):
         "cmpc_sim_gains_download": ([c_void, P(dbl), P(i32)], ctypes.c_int),
         "cmpc_sim_gains_record": ([c_void], c_void),
         "cmpc_sim_gains_status": ([c_void], c_void),
+        "cmpc_freq_check": ([ctypes.c_int, ctypes.c_int, P(i32), ctypes.c_int, P(i32), ctypes.c_int, P(dbl)],
+                            ctypes.c_int),
+        "cmpc_plant_freq_host": ([ctypes.c_int, ctypes.c_int, P(dbl), P(dbl), P(dbl), ctypes.c_int, P(i32),
+                                  ctypes.c_int, P(i32), ctypes.c_int, P(dbl), P(dbl), P(dbl), P(i32)], ctypes.c_int),
+        "cmpc_freq_host": ([ctypes.c_int, ctypes.c_int, P(dbl), P(dbl), P(dbl), P(dbl), ctypes.c_int, ctypes.c_int,
+                            ctypes.c_int, P(dbl), P(dbl), P(dbl), P(i32)], ctypes.c_int),
+        "cmpc_sim_freq": ([c_void, ctypes.c_int, P(i32), ctypes.c_int, P(i32), ctypes.c_int, P(dbl)], ctypes.c_int),
+        "cmpc_sim_freq_download": ([c_void, P(dbl), P(dbl), P(i32)], ctypes.c_int),
+        "cmpc_sim_freq_record": ([c_void], c_void),
+        "cmpc_sim_freq_summary": ([c_void], c_void),
+        "cmpc_sim_freq_status": ([c_void], c_void),
         "cmpc_eig_host": ([ctypes.c_int, ctypes.c_int, P(dbl), ctypes.c_int, P(dbl), P(dbl), P(i32), P(i32)],
                           ctypes.c_int),
         "cmpc_eig_device": ([ctypes.c_int, ctypes.c_int, c_void, ctypes.c_int, c_void, c_void, c_void, c_void,

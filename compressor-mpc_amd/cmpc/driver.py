@@ -36,7 +36,7 @@ import numpy as np
 from . import CMPC_TRACE, Context, scenario_limits, scenario_reference_offsets
 from .configs import ControllerConfig
 from .sim import (EQ_MAX_ITER, EQ_TOL, REF_CONTROL_INDEX, REF_DELAYS, REF_EPS, REF_TS, TARGET_TOL_Y,
-                  PlantGains, PlantSimulator)  # noqa: F401
+                  FreqResponse, PlantGains, PlantSimulator)  # noqa: F401
 
 # ClosedLoop.modes: the summary's columns (include/cmpc.h, _abi.MODES_SUMMARY),
 # the eigenvalues and the statuses
@@ -569,6 +569,16 @@ class ClosedLoop:
         array rga and the pressure feed-forward k_ff (B, n, 2), with resid
         (B,) = max|f| and status (B,)."""
         return self.sim.gains(outputs, inputs)
+
+    def freq_response(self, omega, outputs, inputs=(0, 2)) -> "FreqResponse":
+        """The plant's frequency responses at the loop's current states (after
+        trim or trim_to_outputs), under the plant pressures in force
+        (PlantSimulator.freq_response, one launch; nothing of the loop is
+        written): a FreqResponse record of G (B, nw, ny, nu)
+        and Gp (B, nw, ny, 2) complex at the frequencies `omega` (rad/s), the
+        peak magnitude of every entry over the list with the frequency it was
+        found at, resid (B,) = max|f| and status (B,)."""
+        return self.sim.freq_response(omega, outputs, inputs)
 
     def initialize(self, dx_init=None):
         """SimulationSystem(x0, u_offset) + NerveCenter::Initialize(x0, 0,

@@ -9,7 +9,8 @@ import ctypes
 
 import numpy as np
 
-from ._abi import CMPC_EIG_MAX_N, CMPC_GAIN_LEN, CMPC_MODES_NSUM, check, dptr, iptr, load_library
+from ._abi import (CMPC_EIG_MAX_N, CMPC_FREQ_LEN, CMPC_FREQ_MAX_N, CMPC_FREQ_NSUM, CMPC_GAIN_LEN, CMPC_MODES_NSUM,
+                   check, dptr, iptr, load_library)
 
 REF_DELAYS = (0, 40, 0, 40)          # Delays of both plants (control-input order)
 REF_CONTROL_INDEX = (0, 3, 4, 7)     # ControlInputIndex: plant input of each control input
@@ -160,16 +161,111 @@ def plant_gains(plant: int, pressures, u_full, x, outputs, inputs=(0, 2)) -> "Pl
     return _gain_result(record, status, len(o), len(i))
 
 
-def _eig_iter(max_iter, n: int) -> int:
-    """The QR sweeps allowed per matrix: 30 n unless given."""
-    return 30 * n if max_iter is None else int(max_iter)
-
-
 def _complex(wr, wi) -> np.ndarray:
     """wr + i wi with both parts kept bit for bit (a NaN's pattern included)."""
     w = np.empty(wr.shape, np.complex128)
     w.real, w.imag = wr, wi
     return w
+
+
+# plant_freq_response, freq_response, PlantSimulator.freq_response,
+# ClosedLoop.freq_response: the record and the summary of include/cmpc.h sliced
+# to the selection, and both raw (B, nw, CMPC_FREQ_LEN) and (B, CMPC_FREQ_NSUM)
+FreqResponse = collections.namedtuple("FreqResponse", ("G", "Gp", "peak", "peak_omega", "peak_p", "peak_p_omega",
+                                                       "omega", "resid", "status", "record", "summary"))
+
+
+def _freq_list(omega) -> np.ndarray:
+    """omega as a float64 array (nw,); cmpc_freq_check has the rules."""
+    return np.ascontiguousarray(omega, np.float64).reshape(-1)
+
+
+def _freq_result(record, summary, status, omega, ny: int, nu: int) -> "FreqResponse":
+    """The blocks of the record and the summary, sliced to ny and nu; the
+    parts of G and Gp are kept bit for bit (a NaN's pattern included)."""
+    B, nw = record.shape[:2]
+    pairs = record.reshape(B, nw, CMPC_FREQ_LEN // 2, 2)
+    z = _complex(pairs[..., 0], pairs[..., 1])
+    m2, idx = summary[:, 0:24], summary[:, 24:48]
+    with np.errstate(invalid="ignore"):
+        peak = np.sqrt(m2)
+    at = np.full(idx.shape, np.nan)
+    have = ~np.isnan(idx)
+    at[have] = omega[idx[have].astype(np.int64)]
+    return FreqResponse(G=z[:, :, 0:16].reshape(B, nw, 4, 4)[:, :, :ny, :nu],
+                        Gp=z[:, :, 16:24].reshape(B, nw, 4, 2)[:, :, :ny],
+                        peak=peak[:, 0:16].reshape(B, 4, 4)[:, :ny, :nu],
+                        peak_omega=at[:, 0:16].reshape(B, 4, 4)[:, :ny, :nu],
+                        peak_p=peak[:, 16:24].reshape(B, 4, 2)[:, :ny],
+                        peak_p_omega=at[:, 16:24].reshape(B, 4, 2)[:, :ny],
+                        omega=omega, resid=summary[:, 48], status=status, record=record, summary=summary)
+
+
+def plant_freq_response(plant: int, pressures, u_full, x, omega, outputs, inputs=(0, 2)) -> "FreqResponse":
+    """The plant's frequency responses for B scenarios on the host (no device,
+    DESIGN.md §3.23): at x (B, ns), u_full (B, n_inputs) and pressures (B, 2),
+    the response of the linearisation from the control inputs `inputs` (columns
+    of B: 0 and 2 the torques, 1 and 3 the recycle valves) and from (p_in,
+    p_out) to the plant outputs `outputs` at the frequencies `omega` (rad/s,
+    at most 64, each finite and >= 0, any order).  Returns a FreqResponse
+    record: G (B, nw, ny, nu) and Gp (B, nw, ny, 2) complex, peak (B, ny, nu)
+    = max_k |G| with peak_omega the frequency it was found at (the first of
+    equal ones), peak_p and peak_p_omega (B, ny, 2) the same for Gp, omega,
+    resid (B,) = max|f| at x, status (B,), and the raw record (B, nw,
+    CMPC_FREQ_LEN) and summary (B, CMPC_FREQ_NSUM); everything of a scenario is
+    NaN where its status is not CMPC_EQ_OK.  The arithmetic is
+    PlantSimulator.freq_response's, bit for bit."""
+    lib = load_library()
+    ns, ni = _plant_sizes(lib, plant)
+    o = np.ascontiguousarray(outputs, np.int32).reshape(-1)
+    i = np.ascontiguousarray(inputs, np.int32).reshape(-1)
+    w = _freq_list(omega)
+    check(lib.cmpc_freq_check(plant, len(o), iptr(o), len(i), iptr(i), len(w), dptr(w)), "cmpc_freq_check")
+    xs = np.ascontiguousarray(x, np.float64)
+    B = xs.shape[0] if xs.ndim == 2 else 0
+    p = np.ascontiguousarray(pressures, np.float64)
+    u = np.ascontiguousarray(u_full, np.float64)
+    if B < 1 or xs.shape != (B, ns) or p.shape != (B, 2) or u.shape != (B, ni):
+        raise ValueError(f"x must be (B, {ns}), pressures (B, 2) and u_full (B, {ni}), "
+                         f"got {xs.shape}, {p.shape} and {u.shape}")
+    record, summary = np.zeros((B, len(w), CMPC_FREQ_LEN)), np.zeros((B, CMPC_FREQ_NSUM))
+    status = np.zeros(B, np.int32)
+    check(lib.cmpc_plant_freq_host(plant, B, dptr(p), dptr(u), dptr(xs), len(o), iptr(o), len(i), iptr(i), len(w),
+                                   dptr(w), dptr(record), dptr(summary), iptr(status)), "cmpc_plant_freq_host")
+    return _freq_result(record, summary, status, w, len(o), len(i))
+
+
+def freq_response(A, B, C, E, omega) -> "FreqResponse":
+    """C (j w I - A)^-1 [B | E] of matrices given, on the host (cmpc_freq_host,
+    the arithmetic of plant_freq_response from the balancing on): A (n, n), B
+    (n, nu), C (ny, n), E (n, 2), 1 <= n <= 12, ny and nu in [1, 4], or each
+    with a leading batch axis.  Returns a FreqResponse record (resid is 0)."""
+    a = np.asarray(A, np.float64)
+    single = a.ndim == 2
+    a, b, c, e = (np.asarray(m, np.float64)[None] if single else np.asarray(m, np.float64) for m in (A, B, C, E))
+    if a.ndim != 3 or b.ndim != 3 or c.ndim != 3 or e.ndim != 3:
+        raise ValueError("A, B, C and E must all be matrices or all carry one batch axis")
+    nb, n = a.shape[:2]
+    nu, ny = b.shape[2], c.shape[1]
+    if (nb < 1 or not 1 <= n <= CMPC_FREQ_MAX_N or a.shape != (nb, n, n) or b.shape != (nb, n, nu)
+            or c.shape != (nb, ny, n) or e.shape != (nb, n, 2) or not 1 <= nu <= 4 or not 1 <= ny <= 4):
+        raise ValueError(f"A must be (n, n) with 1 <= n <= {CMPC_FREQ_MAX_N}, B (n, nu), C (ny, n) and E (n, 2) with "
+                         f"ny and nu in [1, 4], got {a.shape}, {b.shape}, {c.shape} and {e.shape}")
+    b4, c4 = np.zeros((nb, n, 4)), np.zeros((nb, 4, n))
+    b4[:, :, :nu], c4[:, :ny] = b, c
+    a, e = np.ascontiguousarray(a), np.ascontiguousarray(e)
+    w = _freq_list(omega)
+    record, summary = np.zeros((nb, max(len(w), 1), CMPC_FREQ_LEN)), np.zeros((nb, CMPC_FREQ_NSUM))
+    status = np.zeros(nb, np.int32)
+    check(load_library().cmpc_freq_host(n, nb, dptr(a), dptr(b4), dptr(c4), dptr(e), ny, nu, len(w),
+                                        dptr(w) if len(w) else None, dptr(record), dptr(summary), iptr(status)),
+          "cmpc_freq_host")
+    return _freq_result(record, summary, status, w, ny, nu)
+
+
+def _eig_iter(max_iter, n: int) -> int:
+    """The QR sweeps allowed per matrix: 30 n unless given."""
+    return 30 * n if max_iter is None else int(max_iter)
 
 
 def eig_batch(A, max_iter=None):
@@ -426,6 +522,24 @@ class PlantSimulator:
         record, status = np.zeros((self.B, CMPC_GAIN_LEN)), np.zeros(self.B, np.int32)
         check(self.lib.cmpc_sim_gains_download(self._h, dptr(record), iptr(status)), "cmpc_sim_gains_download")
         return _gain_result(record, status, len(o), len(i))
+
+    def freq_response(self, omega, outputs, inputs=(0, 2)) -> "FreqResponse":
+        """The plant's frequency responses at every scenario's current state,
+        plant input and the pressures in force, at the frequencies `omega`
+        shared by all scenarios (one launch; nothing of the simulator is
+        written).  Returns what plant_freq_response returns, bit for bit; a
+        scenario whose simulator status is nonzero reports CMPC_EQ_SKIPPED with
+        NaN."""
+        o = np.ascontiguousarray(outputs, np.int32).reshape(-1)
+        i = np.ascontiguousarray(inputs, np.int32).reshape(-1)
+        w = _freq_list(omega)
+        check(self.lib.cmpc_sim_freq(self._h, len(o), iptr(o), len(i), iptr(i), len(w), dptr(w) if len(w) else None),
+              "cmpc_sim_freq")
+        record, summary = np.zeros((self.B, len(w), CMPC_FREQ_LEN)), np.zeros((self.B, CMPC_FREQ_NSUM))
+        status = np.zeros(self.B, np.int32)
+        check(self.lib.cmpc_sim_freq_download(self._h, dptr(record), dptr(summary), iptr(status)),
+              "cmpc_sim_freq_download")
+        return _freq_result(record, summary, status, w, len(o), len(i))
 
     def modes(self, max_iter=None):
         """The plant's modes at every scenario's current state, plant input

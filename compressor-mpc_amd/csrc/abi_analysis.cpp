@@ -1,5 +1,5 @@
 // Plant analysis of the C ABI (include/cmpc.h): equilibrium, steady-state
-// target, gains, eigenvalues and modes.  Each has a host form over arrays, a
+// target, gains, frequency responses, eigenvalues and modes.  Each has a host form over arrays, a
 // device form over a simulator's scenarios (cmpc_sim_*) and that form's
 // download.  The only translation unit of the ABI that includes the solvers'
 // shared bodies (*_body.h); its host forms need no device.
@@ -9,6 +9,7 @@
 #include "abi_sim.h"
 #include "eig_body.h"
 #include "equilibrium_body.h"
+#include "freq_body.h"
 #include "gains_body.h"
 #include "target_body.h"
 
@@ -291,6 +292,107 @@ int cmpc_sim_gains_download(cmpc_sim* m, double* record, int32_t* status) {
 
 double* cmpc_sim_gains_record(cmpc_sim* m) { return m ? m->gn_record : nullptr; }
 int32_t* cmpc_sim_gains_status(cmpc_sim* m) { return m ? m->gn_status : nullptr; }
+
+// Plant frequency responses (include/cmpc.h, freq_body.h, freq.hip)
+static int freq_list_check(const char* who, int nw, const double* omega) {
+  if (nw < 1 || nw > cmpc_fq::kMaxNw)
+    return fail(std::string(who) + ": nw must be in [1, " + std::to_string(cmpc_fq::kMaxNw) + "]");
+  if (!omega) return fail(std::string(who) + ": null omega");
+  for (int k = 0; k < nw; ++k)
+    if (!std::isfinite(omega[k]) || omega[k] < 0)
+      return fail(std::string(who) + ": omega[" + std::to_string(k) + "] must be finite and >= 0");
+  return 0;
+}
+
+int cmpc_freq_check(int plant, int ny, const int32_t* out_idx, int nu, const int32_t* in_idx, int nw,
+                    const double* omega) {
+  if (cmpc_gain_check(plant, ny, out_idx, nu, in_idx)) return fail("cmpc_freq_check: " + g_err);
+  return freq_list_check("cmpc_freq_check", nw, omega);
+}
+
+int cmpc_plant_freq_host(int plant, int B, const double* pressures, const double* u_full, const double* x, int ny,
+                         const int32_t* out_idx, int nu, const int32_t* in_idx, int nw, const double* omega,
+                         double* record, double* summary, int32_t* status) {
+  if (cmpc_freq_check(plant, ny, out_idx, nu, in_idx, nw, omega)) return -1;
+  int ns = 0, ni = 0;
+  if (plant_host_args("cmpc_plant_freq_host", plant, B, pressures && u_full && x && record && summary && status, &ns,
+                      &ni))
+    return -1;
+  for (size_t b = 0; b < (size_t)B; ++b)
+    status[b] = for_plant(plant, [&](auto pl) {
+      return cmpc_fq::fq_solve<decltype(pl)::value>(pressures[2 * b], pressures[2 * b + 1], ny, out_idx, nu, in_idx,
+                                         u_full + b * ni, x + b * ns, nw, omega, record + b * nw * CMPC_FREQ_LEN,
+                                         summary + b * CMPC_FREQ_NSUM);
+    });
+  return 0;
+}
+
+int cmpc_freq_host(int n, int B, const double* A, const double* Bm, const double* C, const double* E, int ny, int nu,
+                   int nw, const double* omega, double* record, double* summary, int32_t* status) {
+  if (n < 1 || n > CMPC_FREQ_MAX_N)
+    return fail("cmpc_freq_host: n must be in [1, " + std::to_string(CMPC_FREQ_MAX_N) + "]");
+  if (B < 1) return fail("cmpc_freq_host: B must be >= 1");
+  if (ny < 1 || ny > cmpc_gn::kMaxSel || nu < 1 || nu > cmpc_gn::kMaxSel)
+    return fail("cmpc_freq_host: ny and nu must be in [1, " + std::to_string(cmpc_gn::kMaxSel) + "]");
+  if (freq_list_check("cmpc_freq_host", nw, omega)) return -1;
+  if (!A || !Bm || !C || !E || !record || !summary || !status) return fail("cmpc_freq_host: null argument");
+  const size_t nz = (size_t)n;
+  for (size_t b = 0; b < (size_t)B; ++b)
+    status[b] = cmpc_fq::fq_host(n, A + b * nz * nz, Bm + b * nz * 4, C + b * 4 * nz, E + b * nz * 2, ny, nu, nw, omega,
+                                 record + b * nw * CMPC_FREQ_LEN, summary + b * CMPC_FREQ_NSUM);
+  return 0;
+}
+
+int cmpc_sim_freq(cmpc_sim* m, int ny, const int32_t* out_idx, int nu, const int32_t* in_idx, int nw,
+                  const double* omega_host) {
+  if (!m) return fail("cmpc_sim_freq: null simulator");
+  if (cmpc_freq_check(m->plant, ny, out_idx, nu, in_idx, nw, omega_host)) return -1;
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t Bz = (size_t)m->B;
+  if (ensure_device(&m->fq_omega, sizeof(double) * CMPC_FREQ_MAX_NW) ||
+      ensure_device(&m->fq_summary, sizeof(double) * CMPC_FREQ_NSUM * Bz) ||
+      ensure_device(&m->fq_status, sizeof(int32_t) * Bz))
+    return -1;
+  if (nw > m->fq_cap) {  // (hipFree waits for the work that may still read the old record)
+    if (m->fq_record) HIP_TRY(hipFree(m->fq_record));
+    m->fq_record = nullptr;
+    m->fq_cap = m->fq_nw = 0;
+    HIP_TRY(hipMalloc(&m->fq_record, sizeof(double) * CMPC_FREQ_LEN * Bz * nw));
+    m->fq_cap = nw;
+  }
+  const size_t count = (size_t)nw;
+  if (pinned_upload(m->pin_in, m->stream, m->fq_omega, &omega_host, &count, 1, nullptr)) return -1;
+  FreqParams P;
+  sim_fields(m, &P);
+  P.omega = m->fq_omega;
+  P.record = m->fq_record;
+  P.summary = m->fq_summary;
+  P.status = m->fq_status;
+  P.ny = ny;
+  P.nu = nu;
+  P.nw = nw;
+  for (int j = 0; j < ny; ++j) P.out[j] = out_idx[j];
+  for (int j = 0; j < nu; ++j) P.in[j] = in_idx[j];
+  m->fq_nw = nw;
+  if (cmpc_launch_freq(P, m->plant, m->stream)) return fail("freq launch failed");
+  return check_launch("freq kernel");
+}
+
+int cmpc_sim_freq_download(cmpc_sim* m, double* record, double* summary, int32_t* status) {
+  if (!m) return fail("cmpc_sim_freq_download: null simulator");
+  if (!m->fq_status || m->fq_nw < 1) return fail("cmpc_sim_freq_download: call cmpc_sim_freq first");
+  HIP_TRY(hipSetDevice(m->device));
+  const size_t Bz = (size_t)m->B;
+  // (a span without a host array takes no staging room: the record is the large one)
+  return pinned_download(m->pin_out, m->stream,
+                         {{m->fq_record, record, record ? sizeof(double) * CMPC_FREQ_LEN * Bz * m->fq_nw : 0},
+                          {m->fq_summary, summary, sizeof(double) * CMPC_FREQ_NSUM * Bz},
+                          {m->fq_status, status, sizeof(int32_t) * Bz}});
+}
+
+double* cmpc_sim_freq_record(cmpc_sim* m) { return m ? m->fq_record : nullptr; }
+double* cmpc_sim_freq_summary(cmpc_sim* m) { return m ? m->fq_summary : nullptr; }
+int32_t* cmpc_sim_freq_status(cmpc_sim* m) { return m ? m->fq_status : nullptr; }
 
 // Eigenvalues and plant modes (include/cmpc.h, eig_body.h, eig.hip)
 int cmpc_eig_host(int n, int B, const double* A, int max_iter, double* wr, double* wi, int32_t* status,

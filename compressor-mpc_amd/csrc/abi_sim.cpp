@@ -16,7 +16,8 @@ static void sim_release(cmpc_sim* m) {
   pinned_free(m->pin_out);
   void* bufs[] = {m->x, m->dt, m->u_full, m->u_offset, m->ring, m->scratch, m->stage, m->status, m->own_pr,
                   m->eq_status, m->eq_iters, m->eq_resid, m->tg_status, m->tg_iters, m->tg_resid, m->gn_record,
-                  m->gn_status, m->md_wr, m->md_wi, m->md_summary, m->md_status, m->md_iters};
+                  m->gn_status, m->fq_omega, m->fq_record, m->fq_summary, m->fq_status, m->md_wr, m->md_wi,
+                  m->md_summary, m->md_status, m->md_iters};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (m->own_stream && m->stream) (void)hipStreamDestroy(m->stream);

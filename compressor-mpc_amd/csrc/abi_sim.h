@@ -27,6 +27,11 @@ struct cmpc_sim {
   // results of the last cmpc_sim_gains (record B * CMPC_GAIN_LEN, status B; allocated on first use)
   double* gn_record = nullptr;
   int32_t* gn_status = nullptr;
+  // results of the last cmpc_sim_freq (allocated on first use): the frequencies uploaded (CMPC_FREQ_MAX_NW),
+  // record B * fq_nw * CMPC_FREQ_LEN (room for B * fq_cap frequencies), summary B * CMPC_FREQ_NSUM, status B
+  double *fq_omega = nullptr, *fq_record = nullptr, *fq_summary = nullptr;
+  int32_t* fq_status = nullptr;
+  int fq_nw = 0, fq_cap = 0;
   // results of the last cmpc_sim_modes (allocated on first use): wr, wi B * ns,
   // summary B * CMPC_MODES_NSUM, status and iters B
   double *md_wr = nullptr, *md_wi = nullptr, *md_summary = nullptr;

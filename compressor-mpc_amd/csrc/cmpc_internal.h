@@ -677,6 +677,23 @@ struct GainsParams {
 // four scenarios per wave; -1: unknown plant, ny or nu outside [1, 4], an index
 // outside [0, 4) or a null array
 int cmpc_launch_gains(const GainsParams& P, int plant, void* stream);
+// Plant frequency responses (freq.hip, cmpc_sim_freq)
+struct FreqParams {
+  const double* x;            // B * ns, read only
+  const double* u_full;       // B * n_inputs, read only
+  const int32_t* sim_status;  // B or null: nonzero gives CMPC_EQ_SKIPPED
+  const double* pressures;    // B * 2, [p_in, p_out] per scenario, 16-byte aligned; null: p_in, p_out
+  const double* omega;        // nw frequencies (device), the same for every scenario
+  double* record;             // B * nw * CMPC_FREQ_LEN
+  double* summary;            // B * CMPC_FREQ_NSUM
+  int32_t* status;            // B: CMPC_EQ_*
+  int B, ny, nu, nw;
+  int32_t out[4], in[4];      // selected plant outputs and control inputs (the first ny and nu)
+  double p_in, p_out;
+};
+// four scenarios per wave; -1: unknown plant, ny or nu outside [1, 4], nw
+// outside [1, CMPC_FREQ_MAX_NW], an index outside [0, 4) or a null array
+int cmpc_launch_freq(const FreqParams& P, int plant, void* stream);
 // Eigenvalues and plant modes (eig.hip, cmpc_eig_device, cmpc_sim_modes)
 struct EigParams {
   const double* A;   // B * n * n, row-major blocks

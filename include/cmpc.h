@@ -1352,6 +1352,83 @@ int cmpc_sim_gains(cmpc_sim* sim, int ny, const int32_t* out_idx, int nu, const 
 int cmpc_sim_gains_download(cmpc_sim* sim, double* record /* B*49 */, int32_t* status /* B */);
 double* cmpc_sim_gains_record(cmpc_sim* sim);
 int32_t* cmpc_sim_gains_status(cmpc_sim* sim);
+/* Plant frequency responses: for each scenario the map of its
+ * linearisation at (x, u, p) away from rest, from nu <= 4 control inputs and
+ * from the two boundary pressures to ny <= 4 plant outputs, at nw frequencies
+ * shared by all scenarios.  out_idx, in_idx, A, B, C, f and E = df/dp as for
+ * the gains above; omega[nw]: rad/s, each finite and >= 0, in any order,
+ * repeats allowed, 1 <= nw <= CMPC_FREQ_MAX_NW.  Per scenario A is balanced
+ * once by a diagonal similarity of powers of two (Parlett-Reinsch scaling
+ * without permutation, the rule of the modes' balancing; A <- D^-1 A D,
+ * B <- D^-1 B, E <- D^-1 E, C <- C D, all exact), which keeps partial
+ * pivoting from comparing states of different units against j omega.  Then
+ * per frequency
+ *   G (j w) = C_sel (j w I - A)^-1 B_sel   ny x nu, complex
+ *   Gp(j w) = C_sel (j w I - A)^-1 E       ny x 2,  complex
+ * through one complex adjoint solve (A - j w I)^T Z = C_sel^T on ns rows and
+ * ns + 4 columns (pivot: the first largest |re| + |im|; quotients by Smith's
+ * formula).  Host and device run the same arithmetic (csrc/freq_body.h) and
+ * agree bit for bit.  r_f = max|f_i| is reported and not tested.
+ * The record, CMPC_FREQ_LEN = 48 doubles per scenario and frequency (B x nw x
+ * 48 in all): G 4 x 4 row-major in the order of out_idx x in_idx as (re, im)
+ * pairs, then Gp 4 x 2 as pairs.  The summary, CMPC_FREQ_NSUM = 49 doubles per
+ * scenario: the largest re^2 + im^2 over the list of each of the 16 + 8
+ * entries, then the index k into omega of each of these peaks as a double (the
+ * first of equal ones), then r_f.  An entry outside ny / nu is the quiet NaN
+ * 0x7ff8000000000000.  Statuses, one per scenario:
+ *   CMPC_EQ_OK
+ *   CMPC_EQ_DEADZONE        a selected recycle valve below 2e-2
+ *   CMPC_EQ_NONFINITE       an entry of A, of the selected part of B or C, of
+ *                           f or of E is not finite, before or after scaling
+ *   CMPC_EQ_SINGULAR        a zero or non-finite pivot at any frequency (j w
+ *                           an eigenvalue of A in this arithmetic)
+ *   CMPC_EQ_SKIPPED         the simulator's status was nonzero
+ * and for every status but CMPC_EQ_OK all of the scenario's record and summary
+ * is that NaN.  No status is an error of the call.
+ *   cmpc_freq_check         -1 with a message for everything cmpc_gain_check
+ *                           refuses, nw outside [1, 64], a null omega, or a
+ *                           negative or non-finite frequency (host only)
+ *   cmpc_plant_freq_host    B scenarios on the host, no device: record
+ *                           B x nw x 48, summary B x 49, status B
+ *   cmpc_freq_host          the same arithmetic from the balancing on for B
+ *                           sets of matrices given, 1 <= n <= CMPC_FREQ_MAX_N:
+ *                           A B x n x n, Bm B x n x 4, C B x 4 x n, E B x n x 2,
+ *                           outputs and inputs the first ny rows of C and nu
+ *                           columns of Bm (the others are not read); r_f of
+ *                           the summary is 0.  Host only
+ *   cmpc_sim_freq           the simulator's scenarios on its stream, one
+ *                           launch, at its current x and plant input and the
+ *                           pressures in force; omega a host array, uploaded.
+ *                           The result buffers are allocated on first use and
+ *                           grow when B x nw exceeds what they hold.  Nothing
+ *                           of the simulator is written
+ *   cmpc_sim_freq_download  host copies of the last call's results (any
+ *                           pointer may be NULL; record B x nw x 48 with the
+ *                           last call's nw); synchronises
+ *   cmpc_sim_freq_record, _summary, _status  the device arrays (NULL before
+ *                           the first cmpc_sim_freq); a later call with more
+ *                           frequencies may move the record */
+#define CMPC_FREQ_MAX_NW 64
+#define CMPC_FREQ_MAX_N 12
+#define CMPC_FREQ_LEN 48
+#define CMPC_FREQ_NSUM 49
+int cmpc_freq_check(int plant, int ny, const int32_t* out_idx, int nu, const int32_t* in_idx, int nw,
+                    const double* omega);
+int cmpc_plant_freq_host(int plant, int B, const double* pressures /* B*2 */, const double* u_full /* B*n_inputs */,
+                         const double* x /* B*ns */, int ny, const int32_t* out_idx, int nu, const int32_t* in_idx,
+                         int nw, const double* omega /* nw */, double* record /* B*nw*48 */,
+                         double* summary /* B*49 */, int32_t* status /* B */);
+int cmpc_freq_host(int n, int B, const double* A /* B*n*n */, const double* Bm /* B*n*4 */,
+                   const double* C /* B*4*n */, const double* E /* B*n*2 */, int ny, int nu, int nw,
+                   const double* omega /* nw */, double* record /* B*nw*48 */, double* summary /* B*49 */,
+                   int32_t* status /* B */);
+int cmpc_sim_freq(cmpc_sim* sim, int ny, const int32_t* out_idx, int nu, const int32_t* in_idx, int nw,
+                  const double* omega_host /* nw */);
+int cmpc_sim_freq_download(cmpc_sim* sim, double* record /* B*nw*48 */, double* summary /* B*49 */,
+                           int32_t* status /* B */);
+double* cmpc_sim_freq_record(cmpc_sim* sim);
+double* cmpc_sim_freq_summary(cmpc_sim* sim);
+int32_t* cmpc_sim_freq_status(cmpc_sim* sim);
 /* Plant modes: the eigenvalues of small real nonsymmetric
  * matrices in batches, and on top of them the modes of the plant, that is the
  * eigenvalues of the continuous Jacobian A = df/dx at each scenario's state
